@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — the BASELINE.json metric on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline metric, `ms_per_step`, and the stage / roofline figures that
+come from HIP events inside the timed steps themselves).  `--full` adds the
+sections that take runs of their own: the `ranking` and `test_step`
+evaluations, the `cpu_baseline` oracle steps and, at N > 1, the replica
+check.  `--dump-outputs DIR` writes what the last timed step handed back
+(see dump_outputs) as DIR/<name>.npy.
 
 Metric: scored (positive + negative) triples per second of the training step,
 RotatE FB15k shape (E=14951, R=1345) d=1000 -de, b=1024 per GPU, n=256,
@@ -21,7 +29,8 @@ YAGO3-10 shape (E=123182, R=37) d=1000 -de, b=1024 per GPU, n=1024, with the
 entity table row-partitioned across the ranks (partition.py: reduce-scatter of
 the dense entity gradient to the row owners, shard Adam, all-gather of the rows).
 
-Prints one JSON line (rank 0).  `roofline` is the dominant kernel (the fused
+Prints one JSON line (rank 0).  `ranking`, `test_step` and `cpu_baseline`
+appear with `--full` only.  `roofline` is the dominant kernel (the fused
 row pass) timed live with HIP events on its launch stream, `roofline_entity`
 the entity pass the same way; `step_roofline` sums both kernels' bytes over the
 whole step time.  `traffic` fields are rocprofv3 PMC bytes per launch from the
@@ -139,6 +148,44 @@ class DeviceBatches:
         self.step += 1
         pos, neg, w = self.sets[self.step % len(self.sets)]
         return pos, neg, w, ('head-batch' if self.step % 2 == 0 else 'tail-batch')
+
+
+DUMP_TABLE_BYTES = 15 << 20  # per dumped table; four tables + the losses stay under 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname: str, model, log) -> dict:
+    """What the last timed train_step handed its caller, as <dirname>/<name>.npy:
+    `loss` (float64: positive_sample_loss, negative_sample_loss, loss — the
+    returned log), the updated `entity_embedding` / `relation_embedding` and,
+    when the step keeps them, the dense gradients `entity_grad` /
+    `relation_grad` (float32).  A table over DUMP_TABLE_BYTES is cut to a
+    fixed sample of its rows (sorted, drawn without replacement from
+    numpy's default_rng(DUMP_SEED), the same rows for a parameter and its
+    gradient), so two builds run with the same arguments write arrays that
+    compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+
+    def put(name, arr):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+
+    def table(t):
+        t = t.detach()
+        keep = max(1, DUMP_TABLE_BYTES // (t[0].numel() * 4))
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        return t.float().cpu().numpy()
+
+    put("loss", np.array([log["positive_sample_loss"], log["negative_sample_loss"], log["loss"]], dtype=np.float64))
+    for name, p in (("entity", model.entity_embedding), ("relation", model.relation_embedding)):
+        put(name + "_embedding", table(p))
+        if model.keep_grads and p.grad is not None:
+            put(name + "_grad", table(p.grad))
+    return written
 
 
 def _cpu_model() -> str:
@@ -435,13 +482,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sections beside the headline: ranking, test_step, cpu_baseline, replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline section")
     ap.add_argument("--cpu-budget", type=float, default=90.0,
                     help="seconds after which no further full CPU step starts (two are timed when the first ends sooner)")
     ap.add_argument("--no-stage-timer", action="store_true",
                     help="skip the per-stage HIP events (roofline then comes from the committed rocprof summary)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="fb15k")
-    ap.add_argument("--no-rank", action="store_true", help="skip the config-3 ranking section (rank 0, 1 GPU)")
+    ap.add_argument("--no-rank", action="store_true",
+                    help="with --full: skip the config-3 ranking section (rank 0, 1 GPU)")
     ap.add_argument("--hidden-dim", type=int, default=None,
                     help="override the workload's hidden_dim (diagnostics; the headline is the workload's own)")
     ap.add_argument("--batch", type=int, default=None,
@@ -478,7 +530,9 @@ def main():
     torch.manual_seed(0)
     model = KGEModel("RotatE", E, R, D, GAMMA, double_entity_embedding=True, double_relation_embedding=False)
     erange = model.embedding_range.item()
-    cpu_state = (model.entity_embedding.detach().clone(), model.relation_embedding.detach().clone(), erange)
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
+    cpu_state = (model.entity_embedding.detach().clone(), model.relation_embedding.detach().clone(), erange) \
+        if want_cpu else None
     model = model.to(dev)
     model.fuse_optimizer = os.environ.get("KGE_FUSED_ADAM", "1") == "1"
     model.keep_grads = os.environ.get("KGE_KEEP_GRADS", "1") == "1"
@@ -520,8 +574,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_log = None
     for _ in range(a.steps):
-        KGEModel.train_step(model, opt, it, args)
+        last_log = KGEModel.train_step(model, opt, it, args)
     torch.cuda.synchronize()
     if group is not None:
         dist.barrier()
@@ -535,6 +590,7 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if group is not None and a.full:
         # after the timed steps (outside the clock): every exchange that keeps a
         # replicated table must leave it bit-identical on every rank
         from knowledgegraphembedding_amd.distributed import replicas_disagree, table_fingerprint
@@ -649,10 +705,12 @@ def main():
     fr = [x for x in fr if x is not None]
     if any(f > 1.0 for f in fr):
         print(f"bench.py: a roofline fraction exceeds 1 ({fr}); the byte model is wrong", file=sys.stderr)
-    if rank == 0 and world == 1 and not a.no_rank and a.workload == "fb15k":
+    if a.dump_outputs and rank == 0 and last_log is not None:
+        out["dumped"] = dump_outputs(a.dump_outputs, model, last_log)
+    if a.full and rank == 0 and world == 1 and not a.no_rank and a.workload == "fb15k":
         out["ranking"] = rank_section(dev)
         out["test_step"] = test_step_section(dev)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if want_cpu:
         # the full batch at config 2's n = 256; config 5's n = 1024 at a quarter of the rows (one full
         # step there would hold ~40 GB of temporaries and take minutes)
         out["cpu_baseline"] = cpu_baseline(cpu_state, budget_s=a.cpu_budget, b=B if NNEG <= 256 else B // 4)

@@ -12,5 +12,5 @@ rc=$?
 kill $HB
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python3 -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > "$O/smoke.log" 2>&1 || exit $?
-timeout -k 10 600 python3 bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" || exit $?
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > "$O/bench_driver_window.json" 2> "$O/bench_driver_window.err" || exit $?
+timeout -k 10 600 python3 bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" || exit $?
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > "$O/bench_driver_window.json" 2> "$O/bench_driver_window.err" || exit $?

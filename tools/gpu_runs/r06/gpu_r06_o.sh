@@ -6,4 +6,4 @@ O="$ROOT/gpurun_out/r06o"
 mkdir -p "$O"
 cd "$ROOT"
 timeout -k 10 800 python -u -m pytest tests/test_rank_parity_gpu.py tests/test_edge_gpu.py tests/test_run_gpu.py -m gpu -x -v --timeout 300 --timeout-method thread -p no:cacheprovider > "$O/tests.log" 2>&1 || exit $?
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench.json" 2> "$O/bench.err" || exit $?
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench.json" 2> "$O/bench.err" || exit $?
