@@ -80,6 +80,18 @@ enum kge_status {
  *                     "The reference" is its CPU run: with --cuda its test_step evaluates
  *                     cos / sin and sum(dim=2) with ATen's GPU kernels, whose bits are not
  *                     reproduced here (parity against that configuration is unpinned).
+ *
+ * Alignment.  Every table is a contiguous array of 4-byte aligned floats.  When the row span
+ * (entity_dim; its half for RotatE / ComplEx) is a multiple of 4 and entity_embedding and
+ * relation_embedding are both 16-byte aligned, the kernels read rows in 16-byte slots; any
+ * other table runs the same kernels with single-float slots.  With 16-byte slots the
+ * gradient passes also write grad_entity / grad_relation, and stream a fused optimizer's
+ * param / exp_avg / exp_avg_sq of the entity and relation tables (kge_adam_desc), 16 bytes
+ * at a time: kge_score_backward, kge_train_step* and kge_ship_step return KGE_ERR_ARG,
+ * before any launch, if one of those buffers is not 16-byte aligned (as kge_adam_step does
+ * for its four arrays); relation_trig must then be 16-byte aligned too (kge_rank_filtered*).
+ * With single-float slots none of these needs more than float alignment.  An entity table
+ * that is not 16-byte aligned is ranked by the wave scan (path 3) only.
  */
 typedef struct kge_model_desc {
     int32_t model;
@@ -422,7 +434,8 @@ int kge_rank_filtered(const kge_model_desc *m, int32_t mode, const int64_t *quer
 /*
  * The same with the fast pass chosen (path: 0 auto, 1 split-bf16 MFMA tile —
  * DistMult / ComplEx, 4 fp32 MFMA tile — DistMult / ComplEx with float4-aligned
- * rows, 2 register tile — reduction length % 4 == 0, 3 wave scan; KGE_ERR_ARG
+ * rows, 2 register tile — reduction length % 4 == 0, 3 wave scan; paths 1, 2
+ * and 4 need a 16-byte aligned entity table; KGE_ERR_ARG
  * if the rows do not suit the requested path) and
  * listed_out [nq] int32 (nullable): near-ties re-scored per query (above the
  * 1024-per-query list capacity the query is rescanned exactly).  Every path

@@ -71,6 +71,21 @@ int check_model(const kge_model_desc* m, Geom* g) {
   return KGE_OK;
 }
 
+// With float4 slots (vec = 4) the entity and relation passes store the
+// gradient rows and stream the fused Adam's param / exp_avg / exp_avg_sq 16
+// bytes at a time, so those buffers must be 16-byte aligned like the tables
+// (a NULL pointer passes: whether it may be NULL is the entry's own check;
+// pRotatE's modulus is one float, updated by scalar accesses).
+bool grad_streams_aligned(const Geom& geo, const float* grad_entity, const float* grad_relation,
+                          const kge_adam_desc* adam) {
+  if (geo.vec != 4) return true;
+  if (!aligned16(grad_entity) || !aligned16(grad_relation)) return false;
+  if (adam)
+    for (const kge_adam_tensor* t : {&adam->entity, &adam->relation})
+      if (!aligned16(t->param) || !aligned16(t->exp_avg) || !aligned16(t->exp_avg_sq)) return false;
+  return true;
+}
+
 // Fast counting pass of the filtered ranking (path 0 = auto): the split-bf16
 // MFMA tile for DistMult / ComplEx (path 1; the fp32 MFMA tile, path 4, when
 // the split operands would pass 32-bit buffer offsets), the register tile for
@@ -84,7 +99,9 @@ int rank_path(const kge_model_desc* m, int requested) {
   const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
   const bool al = aligned16(m->entity_embedding);
   // (the MFMA tiles address their operands through 32-bit buffer offsets)
-  const bool x_ok = bil && (uint64_t)xsplit_elems(m->nentity, m->entity_dim) * 2u < 0x7FFFFFF0ull;
+  // (a table whose base is not 16-byte aligned takes the single-float paths
+  // everywhere: the wave scan here, as DESIGN §3 has it for the other kernels)
+  const bool x_ok = bil && al && (uint64_t)xsplit_elems(m->nentity, m->entity_dim) * 2u < 0x7FFFFFF0ull;
   const bool mfma_ok = bil && (m->entity_dim % 4 == 0) && al &&
                        (uint64_t)m->nentity * (uint64_t)m->entity_dim * 4u < 0xFFFFFF00ull;
   // (the register tile's counting pass reads a block's 64 rows — pRotatE:
@@ -592,6 +609,7 @@ int kge_score_backward(const kge_model_desc* m, int32_t mode, const int64_t* pos
   if (mode != KGE_SINGLE && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
   if (!pos || !grad_scores || !grad_entity || !grad_relation || !err_flag || batch < 1 || nneg < 1)
     return KGE_ERR_ARG;
+  if (!grad_streams_aligned(geo, grad_entity, grad_relation, nullptr)) return KGE_ERR_ARG;
   const int64_t* negp = neg;
   int64_t ns = nneg;
   if (mode == KGE_SINGLE) {
@@ -651,6 +669,7 @@ static int train_impl(const kge_model_desc* m, int32_t mode, const int64_t* pos,
       return KGE_ERR_ARG;  // the update is in place on the model's own tables
     if (m->model == KGE_PROTATE && adam->modulus.param && adam->modulus.param != m->modulus) return KGE_ERR_ARG;
   }
+  if (!grad_streams_aligned(geo, grad_entity, grad_relation, adam)) return KGE_ERR_ARG;
   if (!uni_weight && !subsampling_weight) return KGE_ERR_ARG;
   if (m->model == KGE_PROTATE && !grad_modulus && xstage != XS_ROWS_ONLY && !csr_only) return KGE_ERR_ARG;
   if (xstage != XS_NONE && !csr_only && !uni_weight && !weight_sum) return KGE_ERR_ARG;  // the global Σw comes from the caller
@@ -776,6 +795,7 @@ int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh
   if (adam && (!adam->entity.param || !adam->entity.exp_avg || !adam->entity.exp_avg_sq ||
                adam->entity.param != m->entity_embedding))
     return KGE_ERR_ARG;
+  if (!grad_streams_aligned(geo, grad_entity, grad_relation, adam)) return KGE_ERR_ARG;
   size_t need = 0;
   GradWs w = carve_grad(workspace, m, B, n, &need);
   if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
