@@ -1,6 +1,10 @@
 // kge_capi.hip — the extern "C" boundary declared in include/kge_hip.h.
 // Host-side argument checks, workspace carving and launch sequencing; no
 // allocation, no synchronisation (graph-capturable).
+//
+// Layout: shared helpers, then training (StepCall → StepPlan → the rows /
+// entity / finalize phases), then ranking (RankCall → RankRun → table, queries,
+// tail), then the one extern "C" block whose entries fill a call struct by name.
 #include <stdlib.h>
 #include <string.h>
 
@@ -71,6 +75,26 @@ int check_model(const kge_model_desc* m, Geom* g) {
   return KGE_OK;
 }
 
+int kernel_mode(int32_t mode) { return (mode == KGE_HEAD_BATCH) ? HEAD_BATCH : TAIL_BATCH; }
+
+// The candidates of a scoring call.  'single' scores (h, r, t) with the
+// tail-batch formulas, t in place of one negative per row: the ids alias the
+// positives' third column.
+struct Negatives {
+  const int64_t* ids;
+  int64_t stride;  // id of (i, j) = ids[i * stride + j]
+};
+int negatives_of(int32_t mode, const int64_t* pos, const int64_t* neg, int64_t nneg, Negatives* out) {
+  if (mode == KGE_SINGLE) {
+    if (nneg != 1) return KGE_ERR_ARG;
+    *out = {pos + 2, 3};
+  } else {
+    if (!neg) return KGE_ERR_ARG;
+    *out = {neg, nneg};
+  }
+  return KGE_OK;
+}
+
 // With float4 slots (vec = 4) the entity and relation passes store the
 // gradient rows and stream the fused Adam's param / exp_avg / exp_avg_sq 16
 // bytes at a time, so those buffers must be 16-byte aligned like the tables
@@ -85,36 +109,6 @@ bool grad_streams_aligned(const Geom& geo, const float* grad_entity, const float
       if (!aligned16(t->param) || !aligned16(t->exp_avg) || !aligned16(t->exp_avg_sq)) return false;
   return true;
 }
-
-// Fast counting pass of the filtered ranking (path 0 = auto): the split-bf16
-// MFMA tile for DistMult / ComplEx (path 1; the fp32 MFMA tile, path 4, when
-// the split operands would pass 32-bit buffer offsets), the register tile for
-// the others when the reduction length is a multiple of 4, the wave scan
-// otherwise.  Every path ends in the same reference-order refinement, so all
-// give the same ranks.
-enum RankPath : int { RP_AUTO = 0, RP_MFMA = 1, RP_TILE = 2, RP_SCAN = 3, RP_MFMA32 = 4 };
-int rank_path(const kge_model_desc* m, int requested) {
-  const bool bil = (m->model == KGE_DISTMULT || m->model == KGE_COMPLEX);
-  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
-  const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
-  const bool al = aligned16(m->entity_embedding);
-  // (the MFMA tiles address their operands through 32-bit buffer offsets)
-  // (a table whose base is not 16-byte aligned takes the single-float paths
-  // everywhere: the wave scan here, as DESIGN §3 has it for the other kernels)
-  const bool x_ok = bil && al && (uint64_t)xsplit_elems(m->nentity, m->entity_dim) * 2u < 0x7FFFFFF0ull;
-  const bool mfma_ok = bil && (m->entity_dim % 4 == 0) && al &&
-                       (uint64_t)m->nentity * (uint64_t)m->entity_dim * 4u < 0xFFFFFF00ull;
-  // (the register tile's counting pass reads a block's 64 rows — pRotatE:
-  // their 2K-float phase rows — through one buffer descriptor)
-  const bool tile_ok = (K % 4 == 0) && al && (uint64_t)64 * 2 * (uint64_t)m->entity_dim * 4u < 0x7FFFFFF0ull;
-  if (requested == RP_MFMA) return x_ok ? RP_MFMA : -1;
-  if (requested == RP_MFMA32) return mfma_ok ? RP_MFMA32 : -1;
-  if (requested == RP_TILE) return tile_ok ? RP_TILE : -1;
-  if (requested == RP_SCAN) return RP_SCAN;
-  return x_ok ? RP_MFMA : mfma_ok ? RP_MFMA32 : (tile_ok ? RP_TILE : RP_SCAN);
-}
-constexpr int RANK_CAP = KGE_RANK_LIST_CAP;  // listed near-ties per query before the exact rescan takes over
-static_assert(RANK_CAP <= 1024, "k_rank_refine's pRotatE screen holds 4 list entries per thread of 256");
 
 Consts consts_of(const kge_model_desc* m) {
   Consts c;
@@ -137,6 +131,123 @@ struct Carver {
     return p;
   }
 };
+
+hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// Diagnostic switches, read per call so a test can flip them between calls;
+// none changes a result bit (each selects between paths that are tested
+// bitwise equal): KGE_ENT_SLICES (force the entity pass's column-slice count;
+// 0 = the row-per-wave k_entity), KGE_FIN_SEPARATE (the loss finalisation as
+// its own launch), KGE_CSR_SERIAL (the occurrence CSR before the row pass, not
+// beside it), KGE_RANK_SIDE (the ranking's table work on the side stream),
+// KGE_RANK_SIN_SCREEN=0 (pRotatE: send every listed near-tie to the caller's
+// sin, no device screen).
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// ---- timers (bench instrumentation; see kge_stage_timer in the header)
+// Events created on first use and kept; a reset rewinds `used`.
+struct EventPool {
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;  // events recorded so far
+  // records the next event on s; false (and none used up) when that fails
+  bool record(hipStream_t s) {
+    if (used == ev.size()) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return false;
+      ev.push_back(e);
+    }
+    if (hipEventRecord(ev[used], s) != hipSuccess) return false;
+    ++used;
+    return true;
+  }
+};
+
+// the training step's stage timer: TM_COUNT marks per timed call
+enum TimerMark { TM_START, TM_Q_BUILT, TM_ROWS_END, TM_EPI_END, TM_CSR_JOINED, TM_ENTITY_END, TM_END, TM_COUNT };
+static_assert(TM_COUNT == KGE_TIMER_STAGES + 1, "a stage is the time between two marks");
+struct StageTimer {
+  bool on = false;
+  int period = 1;   // time one train call in `period`
+  size_t seen = 0;  // train calls since enabled
+  EventPool pool;
+  void mark(hipStream_t s) {
+    if (on) pool.record(s);
+  }
+  // kge_stage_timer reads the marks in TM_COUNT's: a timed call that runs only
+  // part of the step owes the marks after its last live one
+  void pad_after(hipStream_t s, TimerMark last_live) {
+    for (int k = last_live + 1; k < TM_COUNT; ++k) mark(s);
+  }
+};
+StageTimer g_timer;
+void timer_mark(hipStream_t s) { g_timer.mark(s); }  // RowArgs.timer_mid: TM_Q_BUILT
+
+// the ranking's stage timer (kge_stage_timer commands 4 / 5): marks tagged by
+// slot — 0 the call starts (with the call's number of directions), 1 fast pass
+// begins, 2 fast pass ends, 3 ranks written.  A call is the marks from one
+// slot-0 mark to the next; a stage is the time between the call's first mark of
+// its slot and its last mark of the next slot, so a call that writes ranks in
+// several pieces (pRotatE's per-chunk finish calls each mark slot 3) is timed to
+// its last piece, and the list stage's own calls need no padding.
+struct RankTimer {
+  bool on = false;
+  EventPool pool;
+  std::vector<int> slot, ndir;  // per recorded event
+  void mark(hipStream_t s, int sl, int nd = 1) {
+    if (!on || !pool.record(s)) return;
+    if (slot.size() < pool.used) {
+      slot.resize(pool.used);
+      ndir.resize(pool.used);
+    }
+    slot[pool.used - 1] = sl;
+    ndir[pool.used - 1] = nd;
+  }
+};
+RankTimer g_rank_timer;
+
+// the KGE_TIMER_STAGES stage times of one timed train call (its TM_COUNT
+// events at e), added to ms
+hipError_t add_stage_ms(const hipEvent_t* e, float* ms) {
+  hipError_t err = hipEventSynchronize(e[TM_END]);
+  for (int k = 0; k < KGE_TIMER_STAGES && err == hipSuccess; ++k) {
+    float t = 0.f;
+    err = hipEventElapsedTime(&t, e[k], e[k + 1]);
+    ms[k] += t;
+  }
+  return err;
+}
+
+// ---- side stream: the index-only work (occurrence CSR) and the relation
+// pass run beside the gather kernels of the caller's stream.  Fork/join via
+// events (a pattern stream capture records as graph edges); the caller's
+// stream never runs ahead of anything the side stream still reads or writes.
+struct Side {
+  hipStream_t s = nullptr;
+  hipEvent_t fork = nullptr, csr_done = nullptr, epi_done = nullptr, rel_done = nullptr;
+  hipEvent_t rk_fork = nullptr, rk_join = nullptr;  // ranking: the entity table's statistics / split beside the queries' stages
+};
+
+Side* side_for_device() {
+  static Side sides[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  Side& sd = sides[dev];
+  if (!sd.s) {
+    if (hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
+    hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming);
+    hipEventCreateWithFlags(&sd.csr_done, hipEventDisableTiming);
+    hipEventCreateWithFlags(&sd.epi_done, hipEventDisableTiming);
+    hipEventCreateWithFlags(&sd.rel_done, hipEventDisableTiming);
+    hipEventCreateWithFlags(&sd.rk_fork, hipEventDisableTiming);
+    hipEventCreateWithFlags(&sd.rk_join, hipEventDisableTiming);
+  }
+  return &sd;
+}
+
+// ================================================================ training
 
 struct GradWs {
   float *g, *q, *dq, *ent_contrib, *rel_contrib, *row_stats, *reg_partial, *wsum;
@@ -170,101 +281,61 @@ GradWs carve_grad(void* ws, const kge_model_desc* m, int64_t B, int64_t n, size_
   return w;
 }
 
-hipStream_t as_stream(void* s) { return (hipStream_t)s; }
-
-// ---- stage timer (bench instrumentation; see kge_stage_timer in the header)
-struct StageTimer {
-  bool on = false;
-  int period = 1;              // time one train call in `period`
-  size_t seen = 0;             // train calls since enabled
-  std::vector<hipEvent_t> ev;  // (KGE_TIMER_STAGES + 1) events per timed call
-  size_t used = 0;             // events recorded so far
-  hipEvent_t next(hipStream_t) {
-    if (used == ev.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return nullptr;
-      ev.push_back(e);
-    }
-    return ev[used++];
-  }
-  void mark(hipStream_t s) {
-    if (!on) return;
-    hipEvent_t e = next(s);
-    if (e) hipEventRecord(e, s);
-  }
-};
-StageTimer g_timer;
-void timer_mark(hipStream_t s) { g_timer.mark(s); }
-// the ranking's stage timer (kge_stage_timer commands 4 / 5): marks tagged by
-// slot — 0 the call starts (with the call's number of directions), 1 fast pass
-// begins, 2 fast pass ends, 3 ranks written.  A call is the marks from one
-// slot-0 mark to the next; a stage is the time between the call's first mark of
-// its slot and its last mark of the next slot, so a call that writes ranks in
-// several pieces (pRotatE's per-chunk finish calls each mark slot 3) is timed to
-// its last piece, and the list stage's own calls need no padding.
-struct RankTimer {
-  bool on = false;
-  std::vector<hipEvent_t> ev;
-  std::vector<int> slot, ndir;
-  size_t used = 0;
-  void mark(hipStream_t s, int sl, int nd = 1) {
-    if (!on) return;
-    if (used == ev.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return;
-      ev.push_back(e);
-      slot.push_back(0);
-      ndir.push_back(0);
-    }
-    if (hipEventRecord(ev[used], s) != hipSuccess) return;
-    slot[used] = sl;
-    ndir[used] = nd;
-    ++used;
-  }
-};
-RankTimer g_rank_timer;
-
-// ---- side stream: the index-only work (occurrence CSR) and the relation
-// pass run beside the gather kernels of the caller's stream.  Fork/join via
-// events (a pattern stream capture records as graph edges); the caller's
-// stream never runs ahead of anything the side stream still reads or writes.
-struct Side {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, csr_done = nullptr, epi_done = nullptr, rel_done = nullptr;
-  hipEvent_t rk_fork = nullptr, rk_join = nullptr;  // ranking: the entity table's statistics / split beside the queries' stages
-};
-// Diagnostic switches, read per call so a test can flip them between calls;
-// none changes a result bit (each selects between paths that are tested
-// bitwise equal): KGE_ENT_SLICES (force the entity pass's column-slice count;
-// 0 = the row-per-wave k_entity), KGE_FIN_SEPARATE (the loss finalisation as
-// its own launch), KGE_RANK_SIN_SCREEN=0 (pRotatE: send every listed
-// near-tie to the caller's sin, no device screen).
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-Side* side_for_device() {
-  static Side sides[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  Side& sd = sides[dev];
-  if (!sd.s) {
-    if (hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming);
-    hipEventCreateWithFlags(&sd.csr_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&sd.epi_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&sd.rel_done, hipEventDisableTiming);
-    hipEventCreateWithFlags(&sd.rk_fork, hipEventDisableTiming);
-    hipEventCreateWithFlags(&sd.rk_join, hipEventDisableTiming);
-  }
-  return &sd;
-}
-
 // Data-parallel factor exchange (kge_train_rows_slice / kge_train_step_from_rows)
 // XS_CSR_ONLY: the occurrence CSR of a batch alone, on the caller's stream;
 // XS_FROM_ROWS_CSR: XS_FROM_ROWS with that CSR already in the workspace
 enum XStage : int { XS_NONE = 0, XS_ROWS_ONLY = 1, XS_FROM_ROWS = 2, XS_CSR_ONLY = 3, XS_FROM_ROWS_CSR = 4 };
+
+// One call of the training family as its entry describes it; an entry fills
+// the groups it means and leaves the rest at these defaults.
+struct StepCall {
+  struct {
+    const kge_model_desc* m;
+    int32_t mode;
+    const int64_t *pos, *neg;
+    int64_t batch, nneg;
+  } in;
+  struct {
+    void* workspace;
+    size_t bytes;
+    int32_t* err_flag;
+    void* stream;
+  } ws;
+  struct Loss {
+    const float* subsampling_weight = nullptr;
+    const float* weight_sum = nullptr;  // the caller's Σw (the exchange stages need it)
+    int32_t uni_weight = 1;
+    int64_t uni_batch = 0;  // > 0: the global batch the uni_weight means divide by
+    int32_t adversarial = 1;
+    float adversarial_temperature = 1.f;
+    float regularization = 0.f;
+  } loss;
+  const kge_adam_desc* adam = nullptr;  // the fused optimizer step, or none
+  struct Out {
+    float *entity = nullptr, *relation = nullptr, *modulus = nullptr, *losses = nullptr;
+  } out;
+  int32_t phases = KGE_PHASE_ALL;
+  int64_t e_begin = 0, e_end = -1;  // the entity rows an owner's step covers (-1: to the table's end)
+  int xstage = XS_NONE;
+  struct Rows {  // the exchange stages' per-row factors, in the caller's (gathered) buffers
+    float *g = nullptr, *dq = nullptr, *stats = nullptr;
+  } rows;
+  int reg_relations = 1;             // 0: the caller counts the relation rows' regulariser elsewhere
+  int64_t csr_lo = 0, csr_hi = -1;   // entity buckets the occurrence CSR builds (-1: to the table's end)
+};
+
+// A call's batch as every launch of it sees it.
+struct Batch {
+  const kge_model_desc* m;
+  Geom geo;
+  int kmode;  // HEAD_BATCH / TAIL_BATCH
+  const int64_t* pos;
+  Negatives neg;
+  int64_t B, n;
+  GradWs w;  // (with the caller's buffers in place of the carved ones where a stage brings its own)
+  int32_t* err;
+  hipStream_t s;
+};
 
 // entity pass variant: column slices (k_entity_sl) when the row fits one
 // 16-B slot per lane per slice (returns the slice count); 0 selects the
@@ -309,121 +380,270 @@ int entity_slice_align(int nsl, int S, int Le, const float* ent, const float* gr
   return (S - 64 * (nsl - 1) + max_sh <= 64) ? 1 : 0;
 }
 
-// Shared body of backward and train.  Caller's stream: q build → gather loop →
-// epilogue → entity pass → finalise; side stream: CSR ∥ row pass, relation pass ∥ entity pass.
-int run_grad(const kge_model_desc* m, const Geom& geo, int mode, const int64_t* pos, const int64_t* neg,
-             int64_t neg_stride, int64_t B, int64_t n, RowArgs ra, GradWs w, float* grad_entity,
-             float* grad_relation, float* grad_modulus, float reg, FinArgs fa, const kge_adam_desc* adam,
-             int32_t* err, hipStream_t s, int phases = KGE_PHASE_ALL, int64_t e_begin = 0, int64_t e_end = -1,
-             int xstage = XS_NONE, int reg_relations = 1, int64_t csr_lo = 0, int64_t csr_hi = -1) {
-  const ModelOps& op = ops_for(m->model);
-  AdamK ak;
-  ak.b1 = adam ? adam->beta1 : 0.f;
-  ak.b2 = adam ? adam->beta2 : 0.f;
-  ak.eps = adam ? adam->eps : 0.f;
-  auto adam_t = [&](const kge_adam_tensor* t) {
-    AdamT o;
-    o.p = (adam && t && t->param) ? t->param : nullptr;
-    o.m = o.p ? t->exp_avg : nullptr;
-    o.v = o.p ? t->exp_avg_sq : nullptr;
-    o.step_size = o.p ? t->step_size : 0.f;
-    o.bc2s = o.p ? t->bias_correction2_sqrt : 1.f;
-    return o;
-  };
-  const int write_grad = (!adam || adam->write_grad) ? 1 : 0;
-  const Consts c = consts_of(m);
-  const int Le = m->entity_dim, Lr = m->relation_dim;
-  // k_row's LDS: q (2 padded halves), the merge buffer, the raw scores, the
-  // wave states and, with the fused epilogue, the positive's element terms
-  const bool wide = (geo.ns == 0);  // rows over 2048 floats (kge_wide.inc)
-  const size_t lds = wide ? wide_row_lds(n)
-                          : sizeof(float) * (2 * 64 * (size_t)geo.ns * geo.vec + (size_t)vb_floats(Le) + (size_t)ra.n_lds +
-                                             32 + (ra.fuse_epi ? 64 * (size_t)geo.ns * geo.vec : 0));
-  if (lds > 64 * 1024) return KGE_ERR_DIM;
-  const bool all = (phases == KGE_PHASE_ALL);
-  if (e_end < 0) e_end = m->nentity;
+// ---- argument blocks: one builder each, shared by run_grad and kge_ship_step
+
+AdamK adam_k(const kge_adam_desc* adam) {
+  AdamK k;
+  k.b1 = adam ? adam->beta1 : 0.f;
+  k.b2 = adam ? adam->beta2 : 0.f;
+  k.eps = adam ? adam->eps : 0.f;
+  return k;
+}
+
+AdamT adam_t(const kge_adam_desc* adam, const kge_adam_tensor* t) {
+  AdamT o;
+  o.p = (adam && t && t->param) ? t->param : nullptr;
+  o.m = o.p ? t->exp_avg : nullptr;
+  o.v = o.p ? t->exp_avg_sq : nullptr;
+  o.step_size = o.p ? t->step_size : 0.f;
+  o.bc2s = o.p ? t->bias_correction2_sqrt : 1.f;
+  return o;
+}
+
+// the optimizer's part of a gradient pass's arguments
+struct Opt {
+  AdamT t;         // fused step of this pass's tensor (t.p == null: none)
+  AdamK k;
+  int write_grad;  // store the gradient (always, unless the optimizer is fused and asks not to)
+};
+Opt opt_for(const kge_adam_desc* adam, const kge_adam_tensor* t) {
+  return {adam_t(adam, t), adam_k(adam), (!adam || adam->write_grad) ? 1 : 0};
+}
+// the gradient alone, whatever the call's optimizer (the shipped relation pass)
+const Opt OPT_GRAD_ONLY = {AdamT{}, AdamK{}, 1};
+
+// k_row's LDS: q (2 padded halves), the merge buffer, the raw scores, the
+// wave states and, with the fused epilogue, the positive's element terms;
+// wide rows (kge_wide.inc): one float per negative
+size_t row_lds(const Geom& geo, int Le, const RowArgs& ra, bool wide) {
+  if (wide) return wide_row_lds(ra.n);
+  return sizeof(float) * (2 * 64 * (size_t)geo.ns * geo.vec + (size_t)vb_floats(Le) + (size_t)ra.n_lds + 32 +
+                          (ra.fuse_epi ? 64 * (size_t)geo.ns * geo.vec : 0));
+}
+constexpr size_t LDS_MAX = 64 * 1024;
+
+RowArgs row_args(const Batch& b) {
+  const kge_model_desc* m = b.m;
+  RowArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.ent = m->entity_embedding; ra.rel = m->relation_embedding; ra.modulus = m->modulus;
+  ra.pos = b.pos; ra.neg = b.neg.ids; ra.neg_stride = b.neg.stride;
+  ra.B = b.B; ra.n = b.n; ra.E = m->nentity; ra.R = m->nrelation;
+  ra.Le = m->entity_dim; ra.Lr = m->relation_dim; ra.eg = b.geo.eg; ra.c = consts_of(m);
+  ra.g_out = b.w.g; ra.q_out = b.w.q; ra.dq_out = b.w.dq; ra.ent_contrib = b.w.ent_contrib;
+  ra.rel_contrib = b.w.rel_contrib; ra.row_stats = b.w.row_stats; ra.err = b.err;
+  ra.fuse_epi = 1;  // measured +1 % over the separate k_row_epi launch
+  return ra;
+}
+
+// the occurrence CSR of the batch, entity buckets [e_lo, e_hi)
+CsrArgs csr_args(const Batch& b, int64_t e_lo, int64_t e_hi) {
+  const GradWs& w = b.w;
+  CsrArgs ca;
+  ca.pos = b.pos; ca.neg = b.neg.ids; ca.neg_stride = b.neg.stride;
+  ca.B = b.B; ca.n = b.n; ca.Bn = b.B * b.n; ca.E = b.m->nentity; ca.R = b.m->nrelation;
+  ca.keys = w.keys; ca.cnt = w.cnt; ca.off = w.off; ca.tmp = w.tmp; ca.occ = w.occ; ca.err = b.err;
+  ca.e_lo = e_lo; ca.e_hi = e_hi;
+  ca.scan_tmp = w.scan_tmp; ca.scan_tmp_bytes = w.scan_tmp_bytes;
+  return ca;
+}
+
+// ent_parts: the entity pass's reg_partial slots, which the relation rows' follow
+RelArgs rel_args(const Batch& b, float reg3, int64_t ent_parts, float* grad_relation, const Opt& opt) {
+  const kge_model_desc* m = b.m;
+  RelArgs rl;
+  memset(&rl, 0, sizeof(rl));
+  rl.rel = m->relation_embedding; rl.R = m->nrelation; rl.E = m->nentity; rl.B = b.B; rl.Bn = b.B * b.n;
+  rl.Lr = m->relation_dim;
+  rl.off = b.w.off; rl.occ = b.w.occ; rl.rel_contrib = b.w.rel_contrib; rl.reg3 = reg3;
+  rl.reg_partial = b.w.reg_partial + ent_parts; rl.grad_rel = grad_relation;
+  rl.write_grad = opt.write_grad;
+  rl.adam = opt.t;
+  rl.adamk = opt.k;
+  return rl;
+}
+
+// the entity rows a step covers, as column parts: nsl per row (1 for the
+// row-per-wave pass), and whether the relation rows' regulariser counts here
+struct EntRange {
+  int64_t e_begin, e_end;
+  int nsl;
+  bool reg_relations;
+  int64_t per() const { return nsl > 0 ? nsl : 1; }
+};
+
+// (align_sl, q_sl, the fused relation rows and finalisation stay off: run_grad
+// alone turns them on)
+EntArgs ent_args(const Batch& b, const EntRange& r, const float* g, float reg, float* grad_entity, const Opt& opt) {
+  const kge_model_desc* m = b.m;
+  EntArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.ent = m->entity_embedding; ea.modulus = m->modulus; ea.E = m->nentity; ea.Le = m->entity_dim; ea.eg = b.geo.eg;
+  ea.e_begin = r.e_begin; ea.e_end = r.e_end;
+  ea.c = consts_of(m); ea.off = b.w.off; ea.occ = b.w.occ; ea.Bn = b.B * b.n; ea.n = b.n;
+  ea.g = g;
+  ea.q = b.w.q; ea.ent_contrib = b.w.ent_contrib; ea.reg3 = 3.f * reg; ea.reg_partial = b.w.reg_partial;
+  ea.grad_ent = grad_entity;
+  ea.write_grad = opt.write_grad;
+  ea.nsl = r.nsl;
+  ea.slice_w = r.nsl > 0 ? (b.geo.eg.S + r.nsl - 1) / r.nsl : 0;  // (wide: elements per part)
+  ea.adam = opt.t;
+  ea.adamk = opt.k;
+  ea.B = b.B;
+  ea.rel_blocks = 0;
+  return ea;
+}
+
+// the loss terms of the finalisation (every training form; kge_score_backward has none)
+FinArgs fin_loss(const StepCall::Loss& l, int64_t B, float* losses, const int32_t* err) {
+  FinArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.sub_w = l.subsampling_weight;
+  fa.w_sum = l.weight_sum;
+  fa.B = B;
+  fa.uni_weight = l.uni_weight ? 1 : 0;
+  fa.uni_n = (float)(l.uni_batch > 0 ? l.uni_batch : B);
+  fa.losses = losses;
+  fa.err = err;
+  return fa;
+}
+
+// ... completed by what the step itself decides: the regulariser's partial
+// sums over the entity rows [e_begin, e_end) (all of them unless an owner's
+// range) and, unless counted elsewhere, the relation rows; pRotatE's modulus
+FinArgs fin_args(FinArgs fa, const Batch& b, const EntRange& r, float reg, float* grad_modulus,
+                 const kge_adam_desc* adam) {
+  const kge_model_desc* m = b.m;
+  const int64_t ent_parts = m->nentity * r.per();
+  fa.row_stats = b.w.row_stats;
+  fa.reg_partial = (reg != 0.f) ? b.w.reg_partial : nullptr;
+  fa.reg_a0 = r.e_begin * r.per();
+  fa.reg_a1 = r.e_end * r.per();
+  fa.reg_b0 = ent_parts;
+  fa.reg_b1 = ent_parts + (r.reg_relations ? m->nrelation : 0);
+  fa.regularization = reg;
+  fa.grad_modulus = (m->model == KGE_PROTATE) ? grad_modulus : nullptr;
+  fa.adam = adam_t(adam, (adam && m->model == KGE_PROTATE) ? &adam->modulus : nullptr);
+  fa.adamk = adam_k(adam);
+  return fa;
+}
+
+// ---- run_grad: the shared body of backward and train.  Caller's stream: q
+// build → gather loop → epilogue → entity pass → finalise; side stream: CSR ∥
+// row pass, relation pass ∥ entity pass.
+
+// Every switch of one call, derived once from the call and its batch.
+struct StepPlan {
+  bool wide;  // rows over 2048 floats (kge_wide.inc)
+  size_t lds;
+  bool all;   // the whole step in this call
+  bool from_rows, csr_ready;
   // stage timing: a full call records all 7 marks; a phased ROWS call (the
   // data-parallel path) records the row-pass marks and pads the rest, so the
   // row pass is timed live on every rank either way
-  const bool from_rows = (xstage == XS_FROM_ROWS || xstage == XS_FROM_ROWS_CSR);
-  const bool csr_ready = (xstage == XS_FROM_ROWS_CSR);
-  const bool timed = (phases & KGE_PHASE_ROWS) && !from_rows && xstage != XS_CSR_ONLY && g_timer.on && ra.op == ROW_TRAIN &&
-                     (g_timer.seen++ % (size_t)g_timer.period) == 0;
-  ra.timer_mid = timed ? &timer_mark : nullptr;
-  Side* sd = side_for_device();
-  hipStream_t ss = sd ? sd->s : s;
-  int st;
-
-  // wide rows: WIDE_PARTS column parts per entity (k_entity_w)
-  const int nsl = wide ? WIDE_PARTS : entity_slices(geo, B, Le);
-  const int64_t ent_parts = m->nentity * (int64_t)(nsl > 0 ? nsl : 1);
+  bool timed;
+  Side* sd;
+  hipStream_t ss;  // the side stream (the caller's where there is none)
+  // entity rows [e_begin, e_end) in nsl column slices (wide rows: WIDE_PARTS
+  // column parts per entity, k_entity_w)
+  EntRange ents;
+  int64_t ent_parts;
   // relation pass: as trailing blocks of the sliced entity launch (one call,
   // no stream join); else beside the entity pass on the side stream (always
   // so in phased calls, and for wide rows)
-  const bool rel_fused = all && nsl > 0 && !wide;
+  bool rel_fused, rel_side;
   // slice-major q: k_row also writes q as [slice][row][re | im] so each of
   // the entity pass's q reads is 2 KB contiguous and line-aligned (0.240 ->
   // 0.234 ms at the FB15k shape); the single-call step with even slices only
   // (the line-aligned slices shift a row's columns by its phase, so they are
   // off here)
-  const bool q_slm = all && nsl > 0 && geo.vec == 4 && xstage == XS_NONE && ra.op == ROW_TRAIN &&
-                     (geo.eg.S + nsl - 1) / nsl <= 64;
-  ra.q_sl = q_slm ? w.q_sl : nullptr;
-  ra.q_sl_w = q_slm ? (geo.eg.S + nsl - 1) / nsl : 0;
-  const bool rel_side = sd && !rel_fused;
-  RelArgs rl;
-  memset(&rl, 0, sizeof(rl));
-  rl.rel = m->relation_embedding; rl.R = m->nrelation; rl.E = m->nentity; rl.B = B; rl.Bn = B * n; rl.Lr = Lr;
-  rl.off = w.off; rl.occ = w.occ; rl.rel_contrib = w.rel_contrib; rl.reg3 = 3.f * reg;
-  rl.reg_partial = w.reg_partial + ent_parts; rl.grad_rel = grad_relation;
-  rl.write_grad = write_grad;
-  rl.adam = adam_t(adam ? &adam->relation : nullptr);
-  rl.adamk = ak;
-
-  if (xstage == XS_ROWS_ONLY) {
-    // the negative-row pass alone (q build + k_row), dL/dq to global memory for
-    // the exchange; no epilogue, CSR or relation pass (kge_train_rows_slice)
-    ra.fuse_epi = 0;
-    if (timed) g_timer.mark(s);
-    st = launch_status(op.row(mode, geo.vec, geo.ns, 0, ra, lds, s));
-    if (st) return st;
-    if (timed)
-      for (int k = 0; k < 5; ++k) g_timer.mark(s);  // row-pass end + the stages not in this call
-    return KGE_OK;
-  }
-  CsrArgs ca;
-  ca.pos = pos; ca.neg = neg; ca.neg_stride = neg_stride;
-  ca.B = B; ca.n = n; ca.Bn = B * n; ca.E = m->nentity; ca.R = m->nrelation;
-  ca.keys = w.keys; ca.cnt = w.cnt; ca.off = w.off; ca.tmp = w.tmp; ca.occ = w.occ; ca.err = err;
-  ca.e_lo = csr_lo; ca.e_hi = csr_hi < 0 ? m->nentity : csr_hi;
-  ca.scan_tmp = w.scan_tmp; ca.scan_tmp_bytes = w.scan_tmp_bytes;
-  if (xstage == XS_CSR_ONLY) return launch_status(launch_csr(ca, s));  // kge_train_csr
-  if (from_rows) ra.fuse_epi = 0;  // the epilogue reads the gathered dL/dq (k_row_epi)
-
+  bool q_slm;
   // KGE_CSR_SERIAL=1 (diagnostic, same bits): the CSR on the caller's stream
   // before the row pass instead of beside it — what k_row gains without the
   // side stream's kernels competing for its CU slots
-  const bool csr_serial = !csr_ready && env_int("KGE_CSR_SERIAL", 0) != 0;
-  const bool use_csr = !csr_ready && !csr_serial;
-  if (phases & KGE_PHASE_ROWS) {
-  if (csr_serial) {
+  bool csr_serial;
+  bool use_csr;  // the CSR beside the row pass
+  // the loss finalisation rides in the entity launch's last block when that
+  // launch is the whole rest of the step and writes nothing the finalisation
+  // reads (no regulariser partials, no pRotatE modulus update)
+  bool fin_wanted, fin_fused;
+  float* grad_modulus;  // (pRotatE only)
+};
+
+int plan_step(const StepCall& c, const Batch& b, const RowArgs& ra, StepPlan* out) {
+  const kge_model_desc* m = b.m;
+  const Geom& geo = b.geo;
+  StepPlan p;
+  p.wide = (geo.ns == 0);
+  p.lds = row_lds(geo, m->entity_dim, ra, p.wide);
+  if (p.lds > LDS_MAX) return KGE_ERR_DIM;
+  p.all = (c.phases == KGE_PHASE_ALL);
+  p.from_rows = (c.xstage == XS_FROM_ROWS || c.xstage == XS_FROM_ROWS_CSR);
+  p.csr_ready = (c.xstage == XS_FROM_ROWS_CSR);
+  p.timed = (c.phases & KGE_PHASE_ROWS) && !p.from_rows && c.xstage != XS_CSR_ONLY && g_timer.on && ra.op == ROW_TRAIN &&
+            (g_timer.seen++ % (size_t)g_timer.period) == 0;
+  p.sd = side_for_device();
+  p.ss = p.sd ? p.sd->s : b.s;
+  p.ents.e_begin = c.e_begin;
+  p.ents.e_end = c.e_end < 0 ? m->nentity : c.e_end;
+  p.ents.nsl = p.wide ? WIDE_PARTS : entity_slices(geo, b.B, m->entity_dim);
+  p.ents.reg_relations = c.reg_relations != 0;
+  p.ent_parts = m->nentity * p.ents.per();
+  p.rel_fused = p.all && p.ents.nsl > 0 && !p.wide;
+  p.rel_side = p.sd && !p.rel_fused;
+  p.q_slm = p.all && p.ents.nsl > 0 && geo.vec == 4 && c.xstage == XS_NONE && ra.op == ROW_TRAIN &&
+            (geo.eg.S + p.ents.nsl - 1) / p.ents.nsl <= 64;
+  p.csr_serial = !p.csr_ready && env_int("KGE_CSR_SERIAL", 0) != 0;
+  p.use_csr = !p.csr_ready && !p.csr_serial;
+  p.grad_modulus = (m->model == KGE_PROTATE) ? c.out.modulus : nullptr;
+  const bool fin_reads_step = c.loss.regularization != 0.f ||
+                              adam_t(c.adam, (c.adam && m->model == KGE_PROTATE) ? &c.adam->modulus : nullptr).p;
+  p.fin_wanted = (c.phases & KGE_PHASE_FINALIZE) && (c.out.losses || p.grad_modulus);
+  p.fin_fused = p.fin_wanted && p.all && p.rel_fused && p.ents.e_end > p.ents.e_begin && !fin_reads_step &&
+                env_int("KGE_FIN_SEPARATE", 0) == 0;
+  *out = p;
+  return KGE_OK;
+}
+
+// XS_ROWS_ONLY: the negative-row pass alone (q build + k_row), dL/dq to global
+// memory for the exchange; no epilogue, CSR or relation pass (kge_train_rows_slice)
+int rows_only(const Batch& b, const StepPlan& p, const RowArgs& ra) {
+  if (p.timed) g_timer.mark(b.s);
+  const int st = launch_status(ops_for(b.m->model).row(b.kmode, b.geo.vec, b.geo.ns, RowStage::Pass, ra, p.lds, b.s));
+  if (st) return st;
+  if (p.timed) {
+    g_timer.mark(b.s);
+    g_timer.pad_after(b.s, TM_ROWS_END);
+  }
+  return KGE_OK;
+}
+
+// KGE_PHASE_ROWS: CSR fork, q build and gather loop, epilogue, and the relation
+// pass where it runs beside the entity pass
+int rows_phase(const Batch& b, const StepPlan& p, const RowArgs& ra, const CsrArgs& ca, const RelArgs& rl) {
+  const ModelOps& op = ops_for(b.m->model);
+  const Geom& geo = b.geo;
+  Side* sd = p.sd;
+  hipStream_t s = b.s, ss = p.ss;
+  int st;
+  if (p.csr_serial) {
     st = launch_status(launch_csr(ca, s));
     if (st) return st;
   }
   // fork point: the occurrence CSR needs only the batch indices (recorded
   // before anything else is queued, so the side stream never waits for the
   // row pass)
-  if (sd && use_csr) hipEventRecord(sd->fork, s);
+  if (sd && p.use_csr) hipEventRecord(sd->fork, s);
 
   // q build + gather loop on the caller's stream, launched first so the GPU
   // is on the long kernel while the host queues everything else
-  if (timed) g_timer.mark(s);
+  if (p.timed) g_timer.mark(s);
   // (XS_FROM_ROWS: the row pass ran on the ranks; only q is rebuilt here)
-  st = launch_status(op.row(mode, geo.vec, geo.ns, from_rows ? 2 : 0, ra, lds, s));
+  st = launch_status(op.row(b.kmode, geo.vec, geo.ns, p.from_rows ? RowStage::QOnly : RowStage::Pass, ra, p.lds, s));
   if (st) return st;
-  if (timed) g_timer.mark(s);
+  if (p.timed) g_timer.mark(s);
 
-  if (use_csr) {
+  if (p.use_csr) {
     if (sd) hipStreamWaitEvent(ss, sd->fork, 0);
     st = launch_status(launch_csr(ca, ss));
     if (st) return st;
@@ -431,237 +651,126 @@ int run_grad(const kge_model_desc* m, const Geom& geo, int mode, const int64_t* 
   }
 
   // epilogue (positive score, chain rule)
-  st = launch_status(op.row(mode, geo.vec, geo.ns, 1, ra, lds, s));
+  st = launch_status(op.row(b.kmode, geo.vec, geo.ns, RowStage::Epilogue, ra, p.lds, s));
   if (st) return st;
-  if (timed) g_timer.mark(s);
+  if (p.timed) g_timer.mark(s);
 
   // relation pass on the side stream once the epilogue's contributions exist
-  if (rel_side) {
+  if (p.rel_side) {
     hipEventRecord(sd->epi_done, s);
     hipStreamWaitEvent(ss, sd->epi_done, 0);
     st = launch_status(launch_rel_rows(rl, ss));
     if (st) return st;
     hipEventRecord(sd->rel_done, ss);
-  } else if (!all) {
+  } else if (!p.all) {
     st = launch_status(launch_rel_rows(rl, s));
     if (st) return st;
   }
-  if (timed && !all)
-    for (int k = 0; k < 3; ++k) g_timer.mark(s);  // stages 3-5 not in this call
-  }  // KGE_PHASE_ROWS
+  if (p.timed && !p.all) g_timer.pad_after(s, TM_EPI_END);
+  return KGE_OK;
+}
 
-  fa.row_stats = w.row_stats;
-  fa.reg_partial = (reg != 0.f) ? w.reg_partial : nullptr;
-  {
-    // entity rows [e_begin, e_end) (all of them unless an owner's range) and,
-    // unless the caller counts them elsewhere, the relation rows
-    const int64_t per = ent_parts / (m->nentity > 0 ? m->nentity : 1);
-    fa.reg_a0 = e_begin * per;
-    fa.reg_a1 = e_end * per;
-    fa.reg_b0 = ent_parts;
-    fa.reg_b1 = ent_parts + (reg_relations ? m->nrelation : 0);
-  }
-  fa.regularization = reg;
-  fa.grad_modulus = grad_modulus;
-  fa.adam = adam_t((adam && m->model == KGE_PROTATE) ? &adam->modulus : nullptr);
-  fa.adamk = ak;
-  // the loss finalisation rides in the entity launch's last block when that
-  // launch is the whole rest of the step and writes nothing the finalisation
-  // reads (no regulariser partials, no pRotatE modulus update)
-  const bool fin_wanted = (phases & KGE_PHASE_FINALIZE) && (fa.losses || grad_modulus);
-  const bool fin_fused = fin_wanted && all && rel_fused && e_end > e_begin && !fa.reg_partial && !fa.adam.p &&
-                         env_int("KGE_FIN_SEPARATE", 0) == 0;
-
-  if (phases & KGE_PHASE_ENTITY) {
-  if (sd && use_csr)
-    hipStreamWaitEvent(s, sd->csr_done, 0);  // join 1: the entity pass reads the CSR
-  if (timed) g_timer.mark(s);
-
-  EntArgs ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.ent = m->entity_embedding; ea.modulus = m->modulus; ea.E = m->nentity; ea.Le = Le; ea.eg = geo.eg;
-  ea.e_begin = e_begin; ea.e_end = e_end;
-  ea.c = c; ea.off = w.off; ea.occ = w.occ; ea.Bn = B * n; ea.n = n;
-  ea.g = (ra.op == ROW_TRAIN) ? w.g : ra.g_in;
-  ea.q = w.q; ea.ent_contrib = w.ent_contrib; ea.reg3 = 3.f * reg; ea.reg_partial = w.reg_partial;
-  ea.grad_ent = grad_entity;
-  ea.write_grad = write_grad;
-  ea.nsl = nsl;
-  ea.slice_w = nsl > 0 ? (geo.eg.S + nsl - 1) / nsl : 0;  // (wide: elements per part)
-  ea.adam = adam_t(adam ? &adam->entity : nullptr);
-  ea.adamk = ak;
-  ea.align_sl = (q_slm || wide) ? 0 : entity_slice_align(nsl, geo.eg.S, Le, m->entity_embedding, write_grad ? grad_entity : nullptr, ea.adam);
-  ea.q_sl = q_slm ? w.q_sl : nullptr;
-  ea.rel = rl;
-  ea.B = B;
-  ea.rel_blocks = rel_fused ? (m->nrelation + 3) / 4 : 0;
-  ea.fin = fa;
-  ea.fin_fused = fin_fused ? 1 : 0;
-  if (e_end > e_begin) {
-    st = launch_status(op.entity(mode, geo.vec, geo.ns, ea, s));
+// KGE_PHASE_ENTITY
+int entity_phase(const Batch& b, const StepPlan& p, const EntArgs& ea, const RelArgs& rl) {
+  hipStream_t s = b.s;
+  int st;
+  if (p.sd && p.use_csr) hipStreamWaitEvent(s, p.sd->csr_done, 0);  // join 1: the entity pass reads the CSR
+  if (p.timed) g_timer.mark(s);
+  if (ea.e_end > ea.e_begin) {
+    st = launch_status(ops_for(b.m->model).entity(b.kmode, b.geo.vec, b.geo.ns, ea, s));
     if (st) return st;
-  } else if (rel_fused) {
+  } else if (p.rel_fused) {
     // an owner with no entity rows (a trailing rank of a small table) still
     // owes the relation pass the entity launch would have carried
     st = launch_status(launch_rel_rows(rl, s));
     if (st) return st;
   }
-  if (timed) g_timer.mark(s);
-  }  // KGE_PHASE_ENTITY
-
-  if (!(phases & KGE_PHASE_FINALIZE)) return KGE_OK;
-  if (rel_side) {
-    hipStreamWaitEvent(s, sd->rel_done, 0);  // join 2: everything the side stream wrote
-  } else if (all && !rel_fused) {
-    st = launch_status(launch_rel_rows(rl, s));
-    if (st) return st;
-  }
-  if (fin_wanted && !fin_fused) {
-    st = launch_status(launch_finalize(fa, s));
-    if (st) return st;
-  }
-  if (timed) g_timer.mark(s);
+  if (p.timed) g_timer.mark(s);
   return KGE_OK;
 }
 
-RowArgs row_args(const kge_model_desc* m, const Geom& geo, const int64_t* pos, const int64_t* neg, int64_t ns,
-                 int64_t B, int64_t n, GradWs w, int32_t* err) {
-  RowArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  ra.ent = m->entity_embedding; ra.rel = m->relation_embedding; ra.modulus = m->modulus;
-  ra.pos = pos; ra.neg = neg; ra.neg_stride = ns;
-  ra.B = B; ra.n = n; ra.E = m->nentity; ra.R = m->nrelation;
-  ra.Le = m->entity_dim; ra.Lr = m->relation_dim; ra.eg = geo.eg; ra.c = consts_of(m);
-  ra.g_out = w.g; ra.q_out = w.q; ra.dq_out = w.dq; ra.ent_contrib = w.ent_contrib; ra.rel_contrib = w.rel_contrib;
-  ra.row_stats = w.row_stats; ra.err = err;
-  ra.fuse_epi = 1;  // measured +1 % over the separate k_row_epi launch
-  return ra;
-}
-
-}  // namespace
-}  // namespace kge
-
-using namespace kge;
-
-extern "C" {
-
-const char* kge_version(void) { return "knowledgegraphembedding_amd " KGE_ABI_VERSION " gfx950"; }
-
-const char* kge_status_string(int status) {
-  switch (status) {
-    case KGE_OK: return "ok";
-    case KGE_ERR_MODEL: return "model not supported";
-    case KGE_ERR_MODE: return "mode not supported";
-    case KGE_ERR_SHAPE: return "entity/relation dims inconsistent with the model";
-    case KGE_ERR_ARG: return "invalid argument";
-    case KGE_ERR_WORKSPACE: return "workspace too small";
-    case KGE_ERR_DIM: return "size outside the kernels' range (negatives per row, queries per call, LDS; wide rows under query shipping)";
-    case KGE_ERR_ABI: return "kge_model_desc.struct_size does not match this library (built against another kge_hip.h)";
-    default:
-      if (status >= KGE_ERR_HIP_BASE) return hipGetErrorString((hipError_t)(status - KGE_ERR_HIP_BASE));
-      return "unknown";
+// KGE_PHASE_FINALIZE
+int finalize_phase(const Batch& b, const StepPlan& p, const RelArgs& rl, const FinArgs& fa) {
+  hipStream_t s = b.s;
+  int st;
+  if (p.rel_side) {
+    hipStreamWaitEvent(s, p.sd->rel_done, 0);  // join 2: everything the side stream wrote
+  } else if (p.all && !p.rel_fused) {
+    st = launch_status(launch_rel_rows(rl, s));
+    if (st) return st;
   }
+  if (p.fin_wanted && !p.fin_fused) {
+    st = launch_status(launch_finalize(fa, s));
+    if (st) return st;
+  }
+  if (p.timed) g_timer.mark(s);
+  return KGE_OK;
 }
 
-int kge_score(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
-              int64_t nneg, float* out, int32_t* err_flag, void* stream) {
+// ra: the row pass's arguments; fa: the finalisation's loss terms (fin_loss)
+int run_grad(const StepCall& c, const Batch& b, RowArgs ra, FinArgs fa) {
+  const kge_model_desc* m = b.m;
+  StepPlan p;
+  int st = plan_step(c, b, ra, &p);
+  if (st) return st;
+  const float reg = c.loss.regularization;
+  ra.timer_mid = p.timed ? &timer_mark : nullptr;
+  ra.q_sl = p.q_slm ? b.w.q_sl : nullptr;
+  ra.q_sl_w = p.q_slm ? (b.geo.eg.S + p.ents.nsl - 1) / p.ents.nsl : 0;
+  // no fused epilogue where there is none (rows only), or where it reads the
+  // gathered dL/dq (k_row_epi after the exchange)
+  if (c.xstage == XS_ROWS_ONLY || p.from_rows) ra.fuse_epi = 0;
+  if (c.xstage == XS_ROWS_ONLY) return rows_only(b, p, ra);
+  const CsrArgs ca = csr_args(b, c.csr_lo, c.csr_hi < 0 ? m->nentity : c.csr_hi);
+  if (c.xstage == XS_CSR_ONLY) return launch_status(launch_csr(ca, b.s));  // kge_train_csr
+
+  const RelArgs rl =
+      rel_args(b, 3.f * reg, p.ent_parts, c.out.relation, opt_for(c.adam, c.adam ? &c.adam->relation : nullptr));
+  if (c.phases & KGE_PHASE_ROWS) {
+    st = rows_phase(b, p, ra, ca, rl);
+    if (st) return st;
+  }
+  fa = fin_args(fa, b, p.ents, reg, p.grad_modulus, c.adam);
+  if (c.phases & KGE_PHASE_ENTITY) {
+    const Opt opt = opt_for(c.adam, c.adam ? &c.adam->entity : nullptr);
+    EntArgs ea = ent_args(b, p.ents, (ra.op == ROW_TRAIN) ? b.w.g : ra.g_in, reg, c.out.entity, opt);
+    ea.align_sl = (p.q_slm || p.wide) ? 0
+                                      : entity_slice_align(p.ents.nsl, b.geo.eg.S, m->entity_dim, m->entity_embedding,
+                                                           opt.write_grad ? c.out.entity : nullptr, ea.adam);
+    ea.q_sl = p.q_slm ? b.w.q_sl : nullptr;
+    ea.rel = rl;
+    ea.rel_blocks = p.rel_fused ? (m->nrelation + 3) / 4 : 0;
+    ea.fin = fa;
+    ea.fin_fused = p.fin_fused ? 1 : 0;
+    st = entity_phase(b, p, ea, rl);
+    if (st) return st;
+  }
+  if (!(c.phases & KGE_PHASE_FINALIZE)) return KGE_OK;
+  return finalize_phase(b, p, rl, fa);
+}
+
+// neg: the call's candidates (its negatives, or 'single''s aliased tails); w: its carved workspace
+Batch batch_of(const StepCall& c, const Geom& geo, const Negatives& neg, const GradWs& w) {
+  return {c.in.m, geo, kernel_mode(c.in.mode), c.in.pos, neg, c.in.batch, c.in.nneg, w, c.ws.err_flag,
+          as_stream(c.ws.stream)};
+}
+
+int train_impl(const StepCall& c) {
+  const kge_model_desc* m = c.in.m;
   Geom geo;
   int st = check_model(m, &geo);
   if (st) return st;
-  if (mode != KGE_SINGLE && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (batch == 0 && nneg >= 1) return KGE_OK;  // empty batch: nothing to score (buffers may be empty/NULL)
-  if (!pos || !out || !err_flag || batch < 0 || nneg < 1) return KGE_ERR_ARG;
-  ScoreArgs a;
-  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
-  a.pos = pos;
-  if (mode == KGE_SINGLE) {
-    if (nneg != 1) return KGE_ERR_ARG;
-    a.neg = pos + 2;  // 'single' scores (h, r, t) with the tail-batch formulas, t in place of a negative
-    a.neg_stride = 3;
-  } else {
-    if (!neg) return KGE_ERR_ARG;
-    a.neg = neg;
-    a.neg_stride = nneg;
-  }
-  a.B = batch; a.n = nneg; a.E = m->nentity; a.R = m->nrelation;
-  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = geo.eg; a.c = consts_of(m);
-  a.jpw = nneg < 16 ? nneg : 16;
-  a.out = out; a.err = err_flag;
-  const int64_t units = batch * ((nneg + a.jpw - 1) / a.jpw);
-  const int kmode = (mode == KGE_HEAD_BATCH) ? HEAD_BATCH : TAIL_BATCH;
-  return launch_status(ops_for(m->model).score(kmode, geo.vec, geo.ns, a, units, as_stream(stream)));
-}
-
-size_t kge_backward_workspace_bytes(const kge_model_desc* m, int32_t mode, int64_t batch, int64_t nneg) {
-  (void)mode;
-  size_t b = 0;
-  carve_grad(nullptr, m, batch, nneg, &b);
-  return b;
-}
-
-int kge_score_backward(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
-                       int64_t nneg, const float* grad_scores, float* grad_entity, float* grad_relation,
-                       float* grad_modulus, void* workspace, size_t workspace_bytes, int32_t* err_flag,
-                       void* stream) {
-  Geom geo;
-  int st = check_model(m, &geo);
-  if (st) return st;
-  if (mode != KGE_SINGLE && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!pos || !grad_scores || !grad_entity || !grad_relation || !err_flag || batch < 1 || nneg < 1)
-    return KGE_ERR_ARG;
-  if (!grad_streams_aligned(geo, grad_entity, grad_relation, nullptr)) return KGE_ERR_ARG;
-  const int64_t* negp = neg;
-  int64_t ns = nneg;
-  if (mode == KGE_SINGLE) {
-    if (nneg != 1) return KGE_ERR_ARG;
-    negp = pos + 2;
-    ns = 3;
-  } else if (!neg) {
-    return KGE_ERR_ARG;
-  }
-  size_t need = 0;
-  GradWs w = carve_grad(workspace, m, batch, nneg, &need);
-  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
-  RowArgs ra = row_args(m, geo, pos, negp, ns, batch, nneg, w, err_flag);
-  ra.op = ROW_GIVEN;
-  ra.g_in = grad_scores;
-  ra.n_lds = 0;
-  FinArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.B = batch;
-  fa.uni_weight = 1;
-  fa.uni_n = 1.f;
-  fa.losses = nullptr;
-  const int kmode = (mode == KGE_HEAD_BATCH) ? HEAD_BATCH : TAIL_BATCH;
-  return run_grad(m, geo, kmode, pos, negp, ns, batch, nneg, ra, w, grad_entity, grad_relation,
-                  m->model == KGE_PROTATE ? grad_modulus : nullptr, 0.f, fa, nullptr, err_flag, as_stream(stream));
-}
-
-size_t kge_train_workspace_bytes(const kge_model_desc* m, int64_t batch, int64_t nneg) {
-  size_t b = 0;
-  carve_grad(nullptr, m, batch, nneg, &b);
-  return b;
-}
-
-static int train_impl(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
-                      int64_t nneg, const float* subsampling_weight, const float* weight_sum, int32_t uni_weight,
-                      int64_t uni_batch, int32_t adversarial, float adversarial_temperature, float regularization,
-                      const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
-                      float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream,
-                      int32_t phases = KGE_PHASE_ALL, int64_t e_begin = 0, int64_t e_end = -1, int xstage = XS_NONE,
-                      float* rows_g = nullptr, float* rows_dq = nullptr, float* rows_stats = nullptr,
-                      int reg_relations = 1, int64_t csr_lo = 0, int64_t csr_hi = -1) {
-  Geom geo;
-  int st = check_model(m, &geo);
-  if (st) return st;
-  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (xstage == XS_NONE && (!grad_entity || !grad_relation || !losses_out)) return KGE_ERR_ARG;
-  const bool csr_only = (xstage == XS_CSR_ONLY);
-  const bool from_rows = (xstage == XS_FROM_ROWS || xstage == XS_FROM_ROWS_CSR);
-  if (xstage != XS_NONE && !csr_only && (!rows_g || !rows_dq || !rows_stats)) return KGE_ERR_ARG;
-  if (from_rows && (!grad_entity || !grad_relation || !losses_out)) return KGE_ERR_ARG;
-  if (!pos || !neg || !err_flag || batch < 1 || nneg < 1) return KGE_ERR_ARG;
-  if (adam) {
+  if (c.in.mode != KGE_HEAD_BATCH && c.in.mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  const bool grads_given = c.out.entity && c.out.relation && c.out.losses;
+  const bool rows_given = c.rows.g && c.rows.dq && c.rows.stats;
+  if (c.xstage == XS_NONE && !grads_given) return KGE_ERR_ARG;
+  const bool csr_only = (c.xstage == XS_CSR_ONLY);
+  const bool from_rows = (c.xstage == XS_FROM_ROWS || c.xstage == XS_FROM_ROWS_CSR);
+  const bool exchange = (c.xstage != XS_NONE && !csr_only);  // a stage of the per-row factor exchange
+  if (exchange && !rows_given) return KGE_ERR_ARG;
+  if (from_rows && !grads_given) return KGE_ERR_ARG;
+  if (!c.in.pos || !c.in.neg || !c.ws.err_flag || c.in.batch < 1 || c.in.nneg < 1) return KGE_ERR_ARG;
+  if (const kge_adam_desc* adam = c.adam) {
     if (!adam->entity.param || !adam->entity.exp_avg || !adam->entity.exp_avg_sq || !adam->relation.param ||
         !adam->relation.exp_avg || !adam->relation.exp_avg_sq)
       return KGE_ERR_ARG;
@@ -669,333 +778,79 @@ static int train_impl(const kge_model_desc* m, int32_t mode, const int64_t* pos,
       return KGE_ERR_ARG;  // the update is in place on the model's own tables
     if (m->model == KGE_PROTATE && adam->modulus.param && adam->modulus.param != m->modulus) return KGE_ERR_ARG;
   }
-  if (!grad_streams_aligned(geo, grad_entity, grad_relation, adam)) return KGE_ERR_ARG;
-  if (!uni_weight && !subsampling_weight) return KGE_ERR_ARG;
-  if (m->model == KGE_PROTATE && !grad_modulus && xstage != XS_ROWS_ONLY && !csr_only) return KGE_ERR_ARG;
-  if (xstage != XS_NONE && !csr_only && !uni_weight && !weight_sum) return KGE_ERR_ARG;  // the global Σw comes from the caller
+  if (!grad_streams_aligned(geo, c.out.entity, c.out.relation, c.adam)) return KGE_ERR_ARG;
+  StepCall::Loss loss = c.loss;
+  if (!loss.uni_weight && !loss.subsampling_weight) return KGE_ERR_ARG;
+  if (m->model == KGE_PROTATE && !c.out.modulus && c.xstage != XS_ROWS_ONLY && !csr_only) return KGE_ERR_ARG;
+  if (exchange && !loss.uni_weight && !loss.weight_sum) return KGE_ERR_ARG;  // the global Σw comes from the caller
   size_t need = 0;
-  GradWs w = carve_grad(workspace, m, batch, nneg, &need);
-  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
-  if (xstage != XS_NONE && !csr_only) {  // the exchanged per-row factors live in the caller's (gathered) buffers
-    w.g = rows_g;
-    w.dq = rows_dq;
-    w.row_stats = rows_stats;
+  GradWs w = carve_grad(c.ws.workspace, m, c.in.batch, c.in.nneg, &need);
+  if (!c.ws.workspace || c.ws.bytes < need) return KGE_ERR_WORKSPACE;
+  if (exchange) {  // the exchanged per-row factors live in the caller's (gathered) buffers
+    w.g = c.rows.g;
+    w.dq = c.rows.dq;
+    w.row_stats = c.rows.stats;
   }
-  hipStream_t s = as_stream(stream);
-  const float* wsum = weight_sum;
   float* wsum_out = nullptr;
-  if (!uni_weight && !wsum) {
+  if (!loss.uni_weight && !loss.weight_sum) {
     wsum_out = w.wsum;  // computed by k_build_q's first block, before k_row reads it
-    wsum = w.wsum;
+    loss.weight_sum = w.wsum;
   }
-  const int64_t ub = uni_batch > 0 ? uni_batch : batch;
-  RowArgs ra = row_args(m, geo, pos, neg, nneg, batch, nneg, w, err_flag);
+  const Batch b = batch_of(c, geo, {c.in.neg, c.in.nneg}, w);
+  RowArgs ra = row_args(b);
   ra.op = ROW_TRAIN;
-  ra.adversarial = adversarial ? 1 : 0;
-  ra.adv_T = adversarial_temperature;
-  ra.uni_weight = uni_weight ? 1 : 0;
-  ra.uni_inv = 1.f / (float)ub;
-  ra.sub_w = subsampling_weight;
-  ra.w_sum = wsum;
+  ra.adversarial = loss.adversarial ? 1 : 0;
+  ra.adv_T = loss.adversarial_temperature;
+  ra.uni_weight = loss.uni_weight ? 1 : 0;
+  ra.uni_inv = 1.f / (float)(loss.uni_batch > 0 ? loss.uni_batch : c.in.batch);
+  ra.sub_w = loss.subsampling_weight;
+  ra.w_sum = loss.weight_sum;
   ra.wsum_out = wsum_out;
-  ra.n_lds = (int)nneg;
-  if (nneg > 8192) return KGE_ERR_DIM;
-  FinArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.sub_w = subsampling_weight;
-  fa.w_sum = wsum;
-  fa.B = batch;
-  fa.uni_weight = uni_weight ? 1 : 0;
-  fa.uni_n = (float)ub;
-  fa.losses = losses_out;
-  fa.err = err_flag;
-  if (phases < 1 || phases > KGE_PHASE_ALL) return KGE_ERR_ARG;
-  if (e_end < 0) e_end = m->nentity;
-  if (e_begin < 0 || e_begin > e_end || e_end > m->nentity) return KGE_ERR_ARG;
-  return run_grad(m, geo, mode, pos, neg, nneg, batch, nneg, ra, w, grad_entity, grad_relation,
-                  m->model == KGE_PROTATE ? grad_modulus : nullptr, regularization, fa, adam, err_flag, s, phases,
-                  e_begin, e_end, xstage, reg_relations, csr_lo, csr_hi);
+  ra.n_lds = (int)c.in.nneg;
+  if (c.in.nneg > 8192) return KGE_ERR_DIM;
+  if (c.phases < 1 || c.phases > KGE_PHASE_ALL) return KGE_ERR_ARG;
+  const int64_t e_end = c.e_end < 0 ? m->nentity : c.e_end;
+  if (c.e_begin < 0 || c.e_begin > e_end || e_end > m->nentity) return KGE_ERR_ARG;
+  return run_grad(c, b, ra, fin_loss(loss, c.in.batch, c.out.losses, c.ws.err_flag));
 }
 
-int kge_train_rows_slice(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                         int64_t nrows, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
-                         int32_t uni_weight, int64_t uni_batch, int32_t adversarial, float adversarial_temperature,
-                         float* g_out, float* dq_out, float* stats_out, void* workspace, size_t workspace_bytes,
-                         int32_t* err_flag, void* stream) {
-  return train_impl(m, mode, pos, neg, nrows, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial,
-                    adversarial_temperature, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
-                    workspace_bytes, err_flag, stream, KGE_PHASE_ROWS, 0, -1, XS_ROWS_ONLY, g_out, dq_out, stats_out);
+// the range entries check their range before anything else
+bool entity_range_ok(const kge_model_desc* m, int64_t begin, int64_t end) {
+  return begin >= 0 && end >= begin && end <= (m ? m->nentity : 0);
 }
 
-int kge_train_step_from_rows(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                             int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
-                             int32_t uni_weight, int64_t uni_batch, float regularization, const float* g_in,
-                             const float* dq_in, float* stats_inout, const kge_adam_desc* adam, float* grad_entity,
-                             float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
-                             size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, 1, 1.f,
-                    regularization, adam, grad_entity, grad_relation, grad_modulus, losses_out, workspace,
-                    workspace_bytes, err_flag, stream, KGE_PHASE_ALL, 0, -1, XS_FROM_ROWS, const_cast<float*>(g_in),
-                    const_cast<float*>(dq_in), stats_inout);
+// ================================================================= ranking
+
+// Fast counting pass of the filtered ranking (path 0 = auto): the split-bf16
+// MFMA tile for DistMult / ComplEx (path 1; the fp32 MFMA tile, path 4, when
+// the split operands would pass 32-bit buffer offsets), the register tile for
+// the others when the reduction length is a multiple of 4, the wave scan
+// otherwise.  Every path ends in the same reference-order refinement, so all
+// give the same ranks.
+enum RankPath : int { RP_AUTO = 0, RP_MFMA = 1, RP_TILE = 2, RP_SCAN = 3, RP_MFMA32 = 4 };
+int rank_path(const kge_model_desc* m, int requested) {
+  const bool bil = (m->model == KGE_DISTMULT || m->model == KGE_COMPLEX);
+  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
+  const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
+  const bool al = aligned16(m->entity_embedding);
+  // (the MFMA tiles address their operands through 32-bit buffer offsets)
+  // (a table whose base is not 16-byte aligned takes the single-float paths
+  // everywhere: the wave scan here, as DESIGN §3 has it for the other kernels)
+  const bool x_ok = bil && al && (uint64_t)xsplit_elems(m->nentity, m->entity_dim) * 2u < 0x7FFFFFF0ull;
+  const bool mfma_ok = bil && (m->entity_dim % 4 == 0) && al &&
+                       (uint64_t)m->nentity * (uint64_t)m->entity_dim * 4u < 0xFFFFFF00ull;
+  // (the register tile's counting pass reads a block's 64 rows — pRotatE:
+  // their 2K-float phase rows — through one buffer descriptor)
+  const bool tile_ok = (K % 4 == 0) && al && (uint64_t)64 * 2 * (uint64_t)m->entity_dim * 4u < 0x7FFFFFF0ull;
+  if (requested == RP_MFMA) return x_ok ? RP_MFMA : -1;
+  if (requested == RP_MFMA32) return mfma_ok ? RP_MFMA32 : -1;
+  if (requested == RP_TILE) return tile_ok ? RP_TILE : -1;
+  if (requested == RP_SCAN) return RP_SCAN;
+  return x_ok ? RP_MFMA : mfma_ok ? RP_MFMA32 : (tile_ok ? RP_TILE : RP_SCAN);
 }
+constexpr int RANK_CAP = KGE_RANK_LIST_CAP;  // listed near-ties per query before the exact rescan takes over
+static_assert(RANK_CAP <= 1024, "k_rank_refine's pRotatE screen holds 4 list entries per thread of 256");
 
-int kge_train_step_from_rows_range(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                                   int64_t batch, int64_t nneg, const float* subsampling_weight,
-                                   const float* weight_sum, int32_t uni_weight, int64_t uni_batch,
-                                   float regularization, const float* g_in, const float* dq_in, float* stats_inout,
-                                   const kge_adam_desc* adam, float* grad_entity, float* grad_relation,
-                                   float* grad_modulus, float* losses_out, void* workspace, size_t workspace_bytes,
-                                   int32_t* err_flag, void* stream, int64_t entity_begin, int64_t entity_end,
-                                   int32_t csr_ready, int32_t reg_relations) {
-  if (entity_begin < 0 || entity_end < entity_begin || entity_end > (m ? m->nentity : 0)) return KGE_ERR_ARG;
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, 1, 1.f,
-                    regularization, adam, grad_entity, grad_relation, grad_modulus, losses_out, workspace,
-                    workspace_bytes, err_flag, stream, KGE_PHASE_ALL, entity_begin, entity_end,
-                    csr_ready ? XS_FROM_ROWS_CSR : XS_FROM_ROWS, const_cast<float*>(g_in), const_cast<float*>(dq_in),
-                    stats_inout, reg_relations ? 1 : 0);
-}
-
-int kge_train_step_from_rows_phased(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                                    int64_t batch, int64_t nneg, const float* subsampling_weight,
-                                    const float* weight_sum, int32_t uni_weight, int64_t uni_batch,
-                                    float regularization, const float* g_in, const float* dq_in, float* stats_inout,
-                                    const kge_adam_desc* adam, float* grad_entity, float* grad_relation,
-                                    float* grad_modulus, float* losses_out, void* workspace, size_t workspace_bytes,
-                                    int32_t* err_flag, void* stream, int32_t phases, int64_t entity_begin,
-                                    int64_t entity_end, int32_t csr_ready, int32_t reg_relations) {
-  if (phases <= 0 || phases > KGE_PHASE_ALL) return KGE_ERR_ARG;
-  if (entity_begin < 0 || entity_end < entity_begin || entity_end > (m ? m->nentity : 0)) return KGE_ERR_ARG;
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, 1, 1.f,
-                    regularization, adam, grad_entity, grad_relation, grad_modulus, losses_out, workspace,
-                    workspace_bytes, err_flag, stream, phases, entity_begin, entity_end,
-                    csr_ready ? XS_FROM_ROWS_CSR : XS_FROM_ROWS, const_cast<float*>(g_in), const_cast<float*>(dq_in),
-                    stats_inout, reg_relations ? 1 : 0);
-}
-
-int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh, int32_t stage,
-                  const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
-                  float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  Geom geo;
-  int st = check_model(m, &geo);
-  if (st) return st;
-  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!sh || stage < KGE_SHIP_Q || stage > KGE_SHIP_ENTITY || !err_flag) return KGE_ERR_ARG;
-  const int64_t B = sh->batch, n = sh->nneg;
-  if (!sh->pos || !sh->neg || B < 1 || n < 1 || n > 8192) return KGE_ERR_ARG;
-  if (sh->world < 1 || sh->world > 4096 || sh->rank < 0 || sh->rank >= sh->world) return KGE_ERR_ARG;
-  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
-  if (!sh->uni_weight && (!sh->subsampling_weight || !sh->weight_sum)) return KGE_ERR_ARG;
-  const bool head = (mode == KGE_HEAD_BATCH);
-  if (!sh->q || !sh->part || !sh->parts || !sh->scores || !sh->g || !sh->dq || !sh->pstats || !sh->ent_contrib ||
-      !sh->rel_contrib || !sh->row_stats || (head && (!sh->qp || !sh->pq)))
-    return KGE_ERR_ARG;
-  if (stage >= KGE_SHIP_CHAIN && !grad_relation) return KGE_ERR_ARG;
-  if (stage == KGE_SHIP_ENTITY && (!grad_entity || !losses_out || (m->model == KGE_PROTATE && !grad_modulus)))
-    return KGE_ERR_ARG;
-  if (adam && (!adam->entity.param || !adam->entity.exp_avg || !adam->entity.exp_avg_sq ||
-               adam->entity.param != m->entity_embedding))
-    return KGE_ERR_ARG;
-  if (!grad_streams_aligned(geo, grad_entity, grad_relation, adam)) return KGE_ERR_ARG;
-  size_t need = 0;
-  GradWs w = carve_grad(workspace, m, B, n, &need);
-  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
-  hipStream_t s = as_stream(stream);
-  const ModelOps& op = ops_for(m->model);
-  const int kmode = head ? HEAD_BATCH : TAIL_BATCH;
-  const int Le = m->entity_dim, Lr = m->relation_dim;
-
-  RowArgs ra = row_args(m, geo, sh->pos, sh->neg, n, B, n, w, err_flag);
-  ra.op = ROW_TRAIN;
-  ra.adversarial = sh->adversarial ? 1 : 0;
-  ra.adv_T = sh->adversarial_temperature;
-  ra.uni_weight = sh->uni_weight ? 1 : 0;
-  ra.uni_inv = 1.f / (float)(sh->uni_batch > 0 ? sh->uni_batch : B);
-  ra.sub_w = sh->subsampling_weight;
-  ra.w_sum = sh->weight_sum;
-  ra.q_out = sh->q; ra.dq_out = sh->dq; ra.g_out = sh->g;
-  ra.ent_contrib = sh->ent_contrib; ra.rel_contrib = sh->rel_contrib; ra.row_stats = sh->row_stats;
-  ra.n_lds = 0; ra.fuse_epi = 0;
-  ra.sh.own_lo = sh->own_begin; ra.sh.own_hi = sh->own_end;
-  ra.sh.world = sh->world; ra.sh.me = sh->rank;
-  ra.sh.q_in = sh->q; ra.sh.qp_in = sh->qp; ra.sh.qp_out = sh->qp;
-  ra.sh.part_out = sh->part; ra.sh.parts_in = sh->parts; ra.sh.s_out = sh->scores;
-  ra.sh.pq = sh->pq; ra.sh.pstats = sh->pstats;
-  Side* sd = side_for_device();
-
-  if (stage == KGE_SHIP_Q) return launch_status(op.row(kmode, geo.vec, geo.ns, 3, ra, 0, s));
-  if (stage == KGE_SHIP_ROWS) {
-    // the occurrence CSR of the global batch beside the row pass (it needs only the ids)
-    CsrArgs ca;
-    ca.pos = sh->pos; ca.neg = sh->neg; ca.neg_stride = n;
-    ca.B = B; ca.n = n; ca.Bn = B * n; ca.E = m->nentity; ca.R = m->nrelation;
-    ca.keys = w.keys; ca.cnt = w.cnt; ca.off = w.off; ca.tmp = w.tmp; ca.occ = w.occ; ca.err = err_flag;
-    ca.e_lo = sh->own_begin; ca.e_hi = sh->own_end;  // only this shard's rows are visited by its entity pass
-    ca.scan_tmp = w.scan_tmp; ca.scan_tmp_bytes = w.scan_tmp_bytes;
-    hipStream_t ss = sd ? sd->s : s;
-    if (sd) {
-      hipEventRecord(sd->fork, s);
-      hipStreamWaitEvent(ss, sd->fork, 0);
-    }
-    st = launch_status(launch_csr(ca, ss));
-    if (st) return st;
-    if (sd) hipEventRecord(sd->csr_done, ss);
-    const size_t lds = sizeof(float) * (2 * 64 * (size_t)geo.ns * geo.vec + (size_t)vb_floats(Le) + (size_t)ra.n_lds + 32);
-    if (lds > 64 * 1024) return KGE_ERR_DIM;
-    return launch_status(op.row(kmode, geo.vec, geo.ns, 4, ra, lds, s));
-  }
-  if (stage == KGE_SHIP_MERGE) return launch_status(op.row(kmode, geo.vec, geo.ns, 5, ra, 0, s));
-
-  const int nsl = entity_slices(geo, B, Le);
-  const int64_t ent_parts = m->nentity * (int64_t)(nsl > 0 ? nsl : 1);
-  const float reg = sh->regularization;
-  if (stage == KGE_SHIP_CHAIN) {
-    st = launch_status(op.row(kmode, geo.vec, geo.ns, 6, ra, 0, s));
-    if (st) return st;
-    if (sd) hipStreamWaitEvent(s, sd->csr_done, 0);  // the relation pass reads the CSR
-    RelArgs rl;
-    memset(&rl, 0, sizeof(rl));
-    rl.rel = m->relation_embedding; rl.R = m->nrelation; rl.E = m->nentity; rl.B = B; rl.Bn = B * n; rl.Lr = Lr;
-    rl.off = w.off; rl.occ = w.occ; rl.rel_contrib = sh->rel_contrib;
-    rl.reg3 = (sh->rank == 0) ? 3.f * reg : 0.f;  // the relation table is replicated: its regulariser once
-    rl.reg_partial = w.reg_partial + ent_parts; rl.grad_rel = grad_relation;
-    rl.write_grad = 1;
-    return launch_status(launch_rel_rows(rl, s));
-  }
-
-  // KGE_SHIP_ENTITY
-  AdamK ak;
-  ak.b1 = adam ? adam->beta1 : 0.f;
-  ak.b2 = adam ? adam->beta2 : 0.f;
-  ak.eps = adam ? adam->eps : 0.f;
-  auto adam_t = [&](const kge_adam_tensor* t) {
-    AdamT o;
-    o.p = (adam && t && t->param) ? t->param : nullptr;
-    o.m = o.p ? t->exp_avg : nullptr;
-    o.v = o.p ? t->exp_avg_sq : nullptr;
-    o.step_size = o.p ? t->step_size : 0.f;
-    o.bc2s = o.p ? t->bias_correction2_sqrt : 1.f;
-    return o;
-  };
-  EntArgs ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.ent = m->entity_embedding; ea.modulus = m->modulus; ea.E = m->nentity; ea.Le = Le; ea.eg = geo.eg;
-  ea.e_begin = sh->own_begin; ea.e_end = sh->own_end;
-  ea.c = consts_of(m); ea.off = w.off; ea.occ = w.occ; ea.Bn = B * n; ea.n = n;
-  ea.g = sh->g; ea.q = sh->q; ea.ent_contrib = sh->ent_contrib; ea.reg3 = 3.f * reg; ea.reg_partial = w.reg_partial;
-  ea.grad_ent = grad_entity;
-  ea.write_grad = (!adam || adam->write_grad) ? 1 : 0;
-  ea.nsl = nsl;
-  ea.slice_w = nsl > 0 ? (geo.eg.S + nsl - 1) / nsl : 0;  // (wide: elements per part)
-  ea.adam = adam_t(adam ? &adam->entity : nullptr);
-  ea.adamk = ak;
-  ea.B = B;
-  ea.rel_blocks = 0;
-  if (sh->own_end > sh->own_begin) {
-    st = launch_status(op.entity(kmode, geo.vec, geo.ns, ea, s));
-    if (st) return st;
-  }
-  FinArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.row_stats = sh->row_stats;
-  fa.sub_w = sh->subsampling_weight;
-  fa.w_sum = sh->weight_sum;
-  fa.B = B;
-  fa.uni_weight = sh->uni_weight ? 1 : 0;
-  fa.uni_n = (float)(sh->uni_batch > 0 ? sh->uni_batch : B);
-  fa.losses = losses_out;
-  fa.err = err_flag;
-  fa.reg_partial = (reg != 0.f) ? w.reg_partial : nullptr;
-  const int64_t per = nsl > 0 ? nsl : 1;
-  fa.reg_a0 = sh->own_begin * per;
-  fa.reg_a1 = sh->own_end * per;
-  fa.reg_b0 = ent_parts;
-  fa.reg_b1 = ent_parts + (sh->rank == 0 ? m->nrelation : 0);
-  fa.regularization = reg;
-  fa.grad_modulus = (m->model == KGE_PROTATE) ? grad_modulus : nullptr;
-  fa.adam = adam_t((adam && m->model == KGE_PROTATE) ? &adam->modulus : nullptr);
-  fa.adamk = ak;
-  return launch_status(launch_finalize(fa, s));
-}
-
-int kge_train_csr(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
-                  int64_t nneg, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return train_impl(m, mode, pos, neg, batch, nneg, nullptr, nullptr, 1, 0, 1, 1.f, 0.f, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, workspace, workspace_bytes, err_flag, stream, KGE_PHASE_ALL, 0, -1, XS_CSR_ONLY);
-}
-
-int kge_train_csr_range(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                        int64_t batch, int64_t nneg, int64_t entity_begin, int64_t entity_end, void* workspace,
-                        size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  if (!m || entity_begin < 0 || entity_end < entity_begin || entity_end > m->nentity) return KGE_ERR_ARG;
-  return train_impl(m, mode, pos, neg, batch, nneg, nullptr, nullptr, 1, 0, 1, 1.f, 0.f, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, workspace, workspace_bytes, err_flag, stream, KGE_PHASE_ALL, 0, -1, XS_CSR_ONLY,
-                    nullptr, nullptr, nullptr, 1, entity_begin, entity_end);
-}
-
-int kge_train_step_from_rows_csr(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                                 int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
-                                 int32_t uni_weight, int64_t uni_batch, float regularization, const float* g_in,
-                                 const float* dq_in, float* stats_inout, const kge_adam_desc* adam, float* grad_entity,
-                                 float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
-                                 size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, 1, 1.f,
-                    regularization, adam, grad_entity, grad_relation, grad_modulus, losses_out, workspace,
-                    workspace_bytes, err_flag, stream, KGE_PHASE_ALL, 0, -1, XS_FROM_ROWS_CSR, const_cast<float*>(g_in),
-                    const_cast<float*>(dq_in), stats_inout);
-}
-
-int kge_train_step_grads_phased(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                                int64_t batch, int64_t nneg, const float* subsampling_weight,
-                                const float* weight_sum, int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
-                                float adversarial_temperature, float regularization, float* grad_entity,
-                                float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
-                                size_t workspace_bytes, int32_t* err_flag, void* stream, int32_t phases,
-                                int64_t entity_begin, int64_t entity_end) {
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial,
-                    adversarial_temperature, regularization, nullptr, grad_entity, grad_relation, grad_modulus,
-                    losses_out, workspace, workspace_bytes, err_flag, stream, phases, entity_begin, entity_end);
-}
-
-int kge_train_step_grads(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
-                         int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
-                         int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
-                         float adversarial_temperature, float regularization, float* grad_entity,
-                         float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
-                         size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial,
-                    adversarial_temperature, regularization, nullptr, grad_entity, grad_relation, grad_modulus,
-                    losses_out, workspace, workspace_bytes, err_flag, stream);
-}
-
-int kge_train_step(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
-                   int64_t nneg, const float* subsampling_weight, const float* weight_sum, int32_t uni_weight,
-                   int64_t uni_batch, int32_t adversarial, float adversarial_temperature, float regularization,
-                   const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
-                   float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  if (!adam) return KGE_ERR_ARG;
-  return train_impl(m, mode, pos, neg, batch, nneg, subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial,
-                    adversarial_temperature, regularization, adam, grad_entity, grad_relation, grad_modulus,
-                    losses_out, workspace, workspace_bytes, err_flag, stream);
-}
-
-int kge_weight_sum(const float* w, int64_t n, float* out, void* stream) {
-  if (!w || !out || n < 0) return KGE_ERR_ARG;
-  return launch_status(launch_weight_sum(w, n, out, as_stream(stream)));
-}
-
-int kge_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, float beta1,
-                  float beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || numel < 0) return KGE_ERR_ARG;
-  if (numel == 0) return KGE_OK;
-  if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq)) return KGE_ERR_ARG;
-  return launch_status(launch_adam(param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, eps, step_size,
-                                   bias_correction2_sqrt, as_stream(stream)));
-}
-
-}  // extern "C"
-
-namespace kge {
-namespace {
 struct RankWs {
   int64_t* tag;  // [8] what the table buffers below hold (k_rank_tag), then [3] the pRotatE list tag
   float *q, *qref, *s_true, *sref_true, *sref_hi, *delta, *stats;
@@ -1038,126 +893,196 @@ RankWs carve_rank(void* ws, const kge_model_desc* m, int64_t nq, size_t* bytes) 
   *bytes = c.off + 256;
   return w;
 }
-}  // namespace
-}  // namespace kge
 
-extern "C" {
-
-size_t kge_rank_workspace_bytes(const kge_model_desc* m, int64_t nq) {
-  size_t b = 0;
-  carve_rank(nullptr, m, nq, &b);
-  return b;
-}
-
-}  // extern "C"
-
-namespace kge {
-namespace {
 // Stages of one filtered-ranking call (kge_rank_filtered_ex, and pRotatE's
 // three-call form with the caller's sin): RS_LIST runs everything up to the
 // fast pass's near-tie lists and writes only listed_out; RS_ARGS writes the
 // pRotatE phase sums of the listed items; RS_FINISH refines them with the
 // caller's sin values, rescans overflowed windows and writes the ranks.
-enum { RS_ALL = 0, RS_LIST = 1, RS_ARGS = 2, RS_FINISH = 3 };
+enum RankStage : int { RS_ALL = 0, RS_LIST = 1, RS_ARGS = 2, RS_FINISH = 3 };
 
-int rank_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq, const int64_t* filt_off,
-              const int64_t* filt_ids, int64_t* ranks_out, int32_t* ties_out, int32_t* listed_out, int32_t path,
-              void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream, int stage,
-              const int64_t* item_off, const float* sins, float* args, const int64_t* filt_off2 = nullptr,
-              const int64_t* filt_ids2 = nullptr, int both = 0) {
-  Geom geo;
-  int st = check_model(m, &geo);
-  if (st) return st;
+// One ranking call as its entry describes it.
+struct RankCall {
+  const kge_model_desc* m;
+  int64_t nq;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* err_flag;
+  void* stream;
+  RankStage stage = RS_ALL;
+  int32_t mode = KGE_HEAD_BATCH;
   // both: head-batch then tail-batch of the same queries in one pass (kge_rank_filtered_both);
   // per-query arrays hold 2·nq entries, the head direction's first
-  if (!both && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!err_flag || nq < 0) return KGE_ERR_ARG;
-  if (both && (stage != RS_ALL || !filt_off2)) return KGE_ERR_ARG;
-  if (stage == RS_ALL || stage == RS_LIST) {
-    if (!queries || !filt_off) return KGE_ERR_ARG;
-  }
-  if ((stage == RS_ALL || stage == RS_FINISH) && !ranks_out) return KGE_ERR_ARG;
-  if (stage == RS_LIST && !listed_out) return KGE_ERR_ARG;
-  if (stage == RS_ARGS && (!item_off || !args)) return KGE_ERR_ARG;
-  if (stage == RS_FINISH && (!item_off || !sins)) return KGE_ERR_ARG;
-  if (stage != RS_ALL && m->model != KGE_PROTATE) return KGE_ERR_MODEL;
-  // KGE_RANK_REUSE_TABLE: the workspace already holds this entity table's
-  // statistics and split operands from the previous call (the other direction)
-  const bool reuse = (path & KGE_RANK_REUSE_TABLE) != 0;
-  const bool ftab = (path & KGE_RANK_FILTER_TABLE) != 0;  // filt_off / filt_ids: the whole filter index
-  path &= ~(KGE_RANK_REUSE_TABLE | KGE_RANK_STAGE_LIST | KGE_RANK_FILTER_TABLE);
-  if (path < RP_AUTO || path > RP_MFMA32) return KGE_ERR_ARG;
-  if (nq == 0) return KGE_OK;
-  if (nq > 65535) return KGE_ERR_DIM;  // the bitmap launch puts queries on grid.y
-  const int rp = rank_path(m, path);
-  if (rp < 0) return KGE_ERR_ARG;  // the requested fast pass cannot take these rows
-  // RotatE's reference cos | sin table (read with the row's slot geometry)
-  const float* trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
-  if (trig && geo.vec == 4 && !aligned16(trig)) return KGE_ERR_ARG;
-  const int ndir = both ? 2 : 1;
-  const int64_t nqt = ndir * nq;  // queries in the workspace
-  const int modes[2] = {both ? (int)KGE_HEAD_BATCH : (int)mode, (int)KGE_TAIL_BATCH};
-  const int64_t* const foff[2] = {filt_off, filt_off2};
-  const int64_t* const fids[2] = {filt_ids, filt_ids2};
-  size_t need = 0;
-  RankWs w = carve_rank(workspace, m, nqt, &need);
-  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
-  hipStream_t s = as_stream(stream);
-  // (gt, eq, gtx, eqx, ucnt are zeroed by k_rank_prep: RankArgs.zero_counts)
-  const ModelOps& ops = ops_for(m->model);
-  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
-  const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
-  const int64_t Le = m->entity_dim, W = (m->nentity + 31) / 32;
+  bool both = false;
+  int32_t path = RP_AUTO;  // a RankPath, with the header's KGE_RANK_* flags
+  const int64_t* queries = nullptr;
+  const int64_t *filt_off = nullptr, *filt_ids = nullptr;
+  const int64_t *filt_off_tail = nullptr, *filt_ids_tail = nullptr;  // (both) the tail direction's
+  int64_t* ranks_out = nullptr;
+  int32_t *ties_out = nullptr, *listed_out = nullptr;
+  // pRotatE's three-call form
+  const int64_t* item_off = nullptr;
+  const float* sins = nullptr;
+  float* args = nullptr;
+};
+
+// A validated ranking call: what its stages share.
+struct RankRun {
+  const kge_model_desc* m;
+  Geom geo;
+  const ModelOps* ops;
+  hipStream_t s;
+  RankStage stage;
+  int mode;
+  bool both, reuse, ftab;
+  int rp;  // the fast pass (RankPath)
+  int ndir;
+  int64_t nq, nqt;  // queries per direction, and in the workspace
+  int modes[2];
+  const int64_t* queries;
+  const int64_t* foff[2];
+  const int64_t* fids[2];
+  const float* trig;  // RotatE's reference cos | sin table (read with the row's slot geometry)
+  int32_t* err;
+  RankWs w;
+  int K;
+  int64_t Le, W;
+  bool prot_tile;  // pRotatE on the register tile (its phase tables)
+  // s_true in the reference's order after the window (k_rank_true_ref):
+  // the split-bf16 path (instead of its gather pass), RotatE and pRotatE on
+  // the register tile (after its gather pass, whose fast s_true sizes the
+  // window's S; pRotatE: a point of the reference score's interval, the
+  // window widened by its width); the window then covers the candidate's
+  // error only
+  bool true_ref;
   RankWin win;
-  win.delta = w.delta; win.ucnt = w.ucnt; win.ulist = w.ulist; win.cap = RANK_CAP;
+  RankArgs a;   // 1. q, true ids (and, for the wave scan, s_true)
+  RefArgs ra;   // the refinement's arguments (steps 4 and 6)
+  EmitArgs ea;
+
   // the per-query arrays of direction d start o = d·nq entries in
-  auto win_at = [&](int64_t o) {
+  RankWin win_at(int64_t o) const {
     RankWin x = win;
     x.delta += o; x.ucnt += o; x.ulist += o * RANK_CAP;
     return x;
-  };
-
-  // 1. q, true ids (and, for the wave scan, s_true)
-  RankArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
-  a.queries = queries; a.nq = nq; a.E = m->nentity; a.R = m->nrelation;
-  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = geo.eg; a.c = consts_of(m);
-  a.filt_off = filt_off; a.filt_ids = filt_ids;
-  a.cpw = 64;
-  a.q = w.q; a.s_true = w.s_true; a.true_id = w.true_id; a.gt = w.gt;
-  a.fbits = w.bits; a.W = W; a.win = win; a.err = err_flag;
-  a.prep_only = 1;
-  a.zero_counts = 1;
-  a.cstride = nqt;
-  a.trig = trig;
-  auto rank_at = [&](int d) {
+  }
+  RankArgs rank_at(int d) const {
     RankArgs x = a;
     const int64_t o = d * nq;
     x.q += o * Le; x.s_true += o; x.true_id += o; x.gt += o; x.fbits += o * W; x.win = win_at(o);
     x.filt_off = foff[d]; x.filt_ids = fids[d];
     return x;
-  };
-  // the refinement's arguments (stages 4 and 6)
-  RefArgs ra;
+  }
+  // a refinement stage: both directions' queries in one launch when both
+  // (each block wholly in one direction, kge_kernels.inc ref_dir)
+  int ref_stage(RefStage st) const { return launch_status(ops->rank_ref(both ? BOTH_DIRS : mode, st, ra, s)); }
+  // one launch per direction of a mode-dependent stage (one direction unless both)
+  template <typename F>
+  int per_dir(F&& launch) const {
+    for (int d = 0; d < ndir; ++d) {
+      const int r = launch(d, modes[d]);
+      if (r) return r;
+    }
+    return KGE_OK;
+  }
+};
+
+// Argument checks and the workspace, in the order tests/test_capi_status.py
+// pins.  An empty call (nq == 0) returns KGE_OK with nothing left to do.
+int rank_validate(const RankCall& c, RankRun* r) {
+  const kge_model_desc* m = c.m;
+  int st = check_model(m, &r->geo);
+  if (st) return st;
+  if (!c.both && c.mode != KGE_HEAD_BATCH && c.mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!c.err_flag || c.nq < 0) return KGE_ERR_ARG;
+  if (c.both && (c.stage != RS_ALL || !c.filt_off_tail)) return KGE_ERR_ARG;
+  if (c.stage == RS_ALL || c.stage == RS_LIST) {
+    if (!c.queries || !c.filt_off) return KGE_ERR_ARG;
+  }
+  if ((c.stage == RS_ALL || c.stage == RS_FINISH) && !c.ranks_out) return KGE_ERR_ARG;
+  if (c.stage == RS_LIST && !c.listed_out) return KGE_ERR_ARG;
+  if (c.stage == RS_ARGS && (!c.item_off || !c.args)) return KGE_ERR_ARG;
+  if (c.stage == RS_FINISH && (!c.item_off || !c.sins)) return KGE_ERR_ARG;
+  if (c.stage != RS_ALL && m->model != KGE_PROTATE) return KGE_ERR_MODEL;
+  // KGE_RANK_REUSE_TABLE: the workspace already holds this entity table's
+  // statistics and split operands from the previous call (the other direction)
+  r->reuse = (c.path & KGE_RANK_REUSE_TABLE) != 0;
+  r->ftab = (c.path & KGE_RANK_FILTER_TABLE) != 0;  // filt_off / filt_ids: the whole filter index
+  const int path = c.path & ~(KGE_RANK_REUSE_TABLE | KGE_RANK_STAGE_LIST | KGE_RANK_FILTER_TABLE);
+  if (path < RP_AUTO || path > RP_MFMA32) return KGE_ERR_ARG;
+  if (c.nq == 0) return KGE_OK;
+  if (c.nq > 65535) return KGE_ERR_DIM;  // the bitmap launch puts queries on grid.y
+  r->rp = rank_path(m, path);
+  if (r->rp < 0) return KGE_ERR_ARG;  // the requested fast pass cannot take these rows
+  r->trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
+  if (r->trig && r->geo.vec == 4 && !aligned16(r->trig)) return KGE_ERR_ARG;
+  r->ndir = c.both ? 2 : 1;
+  r->nq = c.nq;
+  r->nqt = r->ndir * c.nq;
+  size_t need = 0;
+  r->w = carve_rank(c.workspace, m, r->nqt, &need);
+  if (!c.workspace || c.workspace_bytes < need) return KGE_ERR_WORKSPACE;
+  return KGE_OK;
+}
+
+// the argument blocks of a validated call
+void rank_bind(const RankCall& c, RankRun* r) {
+  const kge_model_desc* m = c.m;
+  const RankWs& w = r->w;
+  r->m = m;
+  r->ops = &ops_for(m->model);
+  r->s = as_stream(c.stream);
+  r->stage = c.stage;
+  r->mode = c.mode;
+  r->both = c.both;
+  r->modes[0] = c.both ? (int)KGE_HEAD_BATCH : (int)c.mode;
+  r->modes[1] = (int)KGE_TAIL_BATCH;
+  r->queries = c.queries;
+  r->foff[0] = c.filt_off; r->foff[1] = c.filt_off_tail;
+  r->fids[0] = c.filt_ids; r->fids[1] = c.filt_ids_tail;
+  r->err = c.err_flag;
+  // (gt, eq, gtx, eqx, ucnt are zeroed by k_rank_prep: RankArgs.zero_counts)
+  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
+  r->K = cplx ? m->entity_dim / 2 : m->entity_dim;
+  r->Le = m->entity_dim;
+  r->W = (m->nentity + 31) / 32;
+  r->prot_tile = m->model == KGE_PROTATE && r->rp == RP_TILE;
+  r->true_ref = r->rp == RP_MFMA || (r->rp == RP_TILE && (m->model == KGE_ROTATE || r->prot_tile));
+  r->win.delta = w.delta; r->win.ucnt = w.ucnt; r->win.ulist = w.ulist; r->win.cap = RANK_CAP;
+
+  RankArgs& a = r->a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.queries = c.queries; a.nq = c.nq; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = r->geo.eg; a.c = consts_of(m);
+  a.filt_off = c.filt_off; a.filt_ids = c.filt_ids;
+  a.cpw = 64;
+  a.q = w.q; a.s_true = w.s_true; a.true_id = w.true_id; a.gt = w.gt;
+  a.fbits = w.bits; a.W = r->W; a.win = r->win; a.err = c.err_flag;
+  a.prep_only = 1;
+  a.zero_counts = 1;
+  a.cstride = r->nqt;
+  a.trig = r->trig;
+
+  RefArgs& ra = r->ra;
   memset(&ra, 0, sizeof(ra));
   ra.ent = m->entity_embedding; ra.rel = m->relation_embedding; ra.modulus = m->modulus;
-  ra.queries = queries; ra.nq = nq; ra.E = m->nentity; ra.R = m->nrelation;
-  ra.Le = m->entity_dim; ra.Lr = m->relation_dim; ra.K = K; ra.c = a.c;
+  ra.queries = c.queries; ra.nq = c.nq; ra.E = m->nentity; ra.R = m->nrelation;
+  ra.Le = m->entity_dim; ra.Lr = m->relation_dim; ra.K = r->K; ra.c = a.c;
   ra.q = w.q; ra.qref = w.qref; ra.true_id = w.true_id; ra.s_true = w.s_true; ra.sref_true = w.sref_true;
   ra.s_true_w = w.s_true;
   ra.delta = w.delta; ra.stats = w.stats;
-  ra.exact_fast = (m->model == KGE_TRANSE && rp == RP_TILE) ? 1 : 0;
+  ra.exact_fast = (m->model == KGE_TRANSE && r->rp == RP_TILE) ? 1 : 0;
   ra.ucnt = w.ucnt; ra.ulist = w.ulist; ra.cap = RANK_CAP;
-  ra.fbits = w.bits; ra.W = a.W; ra.gt = w.gt; ra.eq = w.eq; ra.gtx = w.gtx; ra.eqx = w.eqx; ra.err = err_flag;
-  ra.trig = trig;
-  ra.item_off = item_off; ra.sins = sins; ra.args = args;
-  ra.lib_sin = (stage != RS_ALL) ? 1 : 0;
+  ra.fbits = w.bits; ra.W = a.W; ra.gt = w.gt; ra.eq = w.eq; ra.gtx = w.gtx; ra.eqx = w.eqx; ra.err = c.err_flag;
+  ra.trig = r->trig;
+  ra.item_off = c.item_off; ra.sins = c.sins; ra.args = c.args;
+  ra.lib_sin = (c.stage != RS_ALL) ? 1 : 0;
   ra.sref_hi = w.sref_hi; ra.done = w.done;
   // the list tag of pRotatE's three-call form: the later stages must name the
   // list stage's mode, nq and table (a reused or switched
   // workspace gave wrong ranks with no error)
-  const int64_t ltag_v[3] = {(int64_t)0x4B47454C00000000ll | (int64_t)mode, nq,
+  const int64_t ltag_v[3] = {(int64_t)0x4B47454C00000000ll | (int64_t)c.mode, c.nq,
                              (int64_t)(uintptr_t)m->entity_embedding};
   ra.ltag = w.tag ? w.tag + 8 : nullptr;
   for (int k = 0; k < 3; ++k) ra.ltag_v[k] = ltag_v[k];
@@ -1165,237 +1090,634 @@ int rank_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
   // final add 1.2, the slab's three chained MFMAs 97.6, the running sum 1.02·nslab; the
   // split's own error is added per query from the pieces' norms (k_rank_window)
   const int64_t xns = xsplit_nslab(m->entity_dim);
-  ra.fast_u = (rp != RP_MFMA) ? 0.f : (float)(98.8 + 1.02 * xns);
-  // a refinement stage: both directions' queries in one launch when both
-  // (each block wholly in one direction, kge_kernels.inc ref_dir)
-  auto ref_stage = [&](int stage_) -> int { return launch_status(ops.rank_ref(both ? BOTH_DIRS : mode, stage_, ra, s)); };
-  // one launch per direction of a mode-dependent stage (one direction unless both)
-  auto per_dir = [&](auto&& launch) -> int {
-    for (int d = 0; d < ndir; ++d) {
-      const int r = launch(d, modes[d]);
-      if (r) return r;
-    }
-    return KGE_OK;
-  };
-  if (stage == RS_ARGS) return launch_status(ops.rank_ref(mode, 3, ra, s));
-  EmitArgs ea;
+  ra.fast_u = (r->rp != RP_MFMA) ? 0.f : (float)(98.8 + 1.02 * xns);
+
+  EmitArgs& ea = r->ea;
   ea.gt = w.gt; ea.eq = w.eq; ea.gtx = w.gtx; ea.eqx = w.eqx; ea.ucnt = w.ucnt; ea.true_id = w.true_id;
-  ea.nq = nqt; ea.cap = RANK_CAP; ea.ranks = ranks_out; ea.ties = ties_out; ea.listed = listed_out;
+  ea.nq = r->nqt; ea.cap = RANK_CAP; ea.ranks = c.ranks_out; ea.ties = c.ties_out; ea.listed = c.listed_out;
   ea.ltag = nullptr;
   for (int k = 0; k < 3; ++k) ea.ltag_v[k] = ltag_v[k];
+}
 
-  if (stage != RS_FINISH) {
-    g_rank_timer.mark(s, 0, ndir);  // (rank timer) 0: the call starts
-    // the entity table's work (tag, statistics, split or phase table) depends
-    // on the table alone.  KGE_RANK_SIDE=1 (diagnostic, same bits) runs it on
-    // the side stream beside the queries' q / bitmap / split (forked here,
-    // joined before the windows read the statistics): measured 1-2 % SLOWER
-    // than one stream (a ~130 µs dispatch gap before the counting tile after
-    // the cross-stream join; profiles/r06/rank), so the default is the
-    // caller's stream, the table's work queued first
-    Side* rsd = env_int("KGE_RANK_SIDE", 0) != 0 ? side_for_device() : nullptr;
-    hipStream_t ts = rsd ? rsd->s : s;
-    if (rsd) hipEventRecord(rsd->rk_fork, s);
-    // the table's statistics and split operands: reused only where the tag
-    // says this workspace already holds them for this table (k_rank_tag)
-    const bool need_stats = (m->model == KGE_DISTMULT || m->model == KGE_COMPLEX || m->model == KGE_PROTATE);
-    // the derived table: split-bf16 operands (kind 1) or pRotatE's phase table
-    // (kind 2, tagged with its divisor's bits)
-    const bool prot_tile = m->model == KGE_PROTATE && rp == RP_TILE;
-    const float kappa = a.c.kappa_p;
-    int64_t kbits = 0;
-    memcpy(&kbits, &kappa, sizeof(kappa));
-    if (rsd) hipStreamWaitEvent(ts, rsd->rk_fork, 0);
-    st = launch_status(launch_rank_tag(w.tag, m->entity_embedding, m->nentity, m->entity_dim, reuse ? 1 : 0,
-                                       need_stats ? 1 : 0, rp == RP_MFMA ? 1 : (prot_tile ? 2 : 0),
-                                       prot_tile ? kbits : 0, ts));
-    if (st) return st;
-    if (rp == RP_MFMA && need_stats) {  // (DistMult, ComplEx) one read of the table for both
-      st = launch_status(launch_split_stats(m->entity_embedding, m->nentity, m->entity_dim, w.es, w.stats, ts,
-                                            w.tag + 5, w.tag + 6));
-      if (st) return st;
-    } else {
-      if (need_stats) {
-        st = launch_status(launch_table_stats(m->entity_embedding, m->nentity, m->entity_dim, w.stats, ts, w.tag + 5));
-        if (st) return st;
-      }
-      if (rp == RP_MFMA) {
-        st = launch_status(launch_split_bf16(m->entity_embedding, m->nentity, m->entity_dim, w.es, ts, w.tag + 6));
-        if (st) return st;
-      }
-    }
-    if (prot_tile) {
-      st = launch_status(launch_prot_phase(m->entity_embedding, m->nentity, K, kappa, 1, w.eph, ts, w.tag + 6));
-      if (st) return st;
-    }
-    if (rsd) hipEventRecord(rsd->rk_join, ts);
-    if (both && geo.ns != 0) {  // both directions' q in one launch (rows ≤ 2048 floats)
-      RankArgs x = a;
-      x.both_dirs = 1;
-      st = launch_status(ops.rank(KGE_HEAD_BATCH, geo.vec, geo.ns, x, s));
-    } else {
-      st = per_dir([&](int d, int md) { return launch_status(ops.rank(md, geo.vec, geo.ns, rank_at(d), s)); });
-    }
-    if (st) return st;
-    // 2. excluded candidates (filtered ids + the true id) as a bitmap (both
-    // directions in one launch where the row fits LDS)
-    st = both ? launch_filter_bits_both(queries, ftab ? 1 : 0, foff[0], fids[0], foff[1], fids[1], w.true_id, nq,
-                                        m->nentity, m->nrelation, w.bits, err_flag, s)
-              : -1;
-    if (st > 0) return launch_status(st);
-    if (st < 0) st = per_dir([&](int d, int md) {
-      const int64_t o = d * nq;
-      if (ftab)
-        return launch_status(launch_filter_bits_tab(queries, md == KGE_HEAD_BATCH ? 1 : 0, foff[d], fids[d],
-                                                    w.true_id + o, nq, m->nentity, m->nrelation, w.bits + o * W,
-                                                    err_flag, s));
-      return launch_status(launch_filter_bits(foff[d], fids[d], w.true_id + o, nq, m->nentity, w.bits + o * W,
-                                              err_flag, s));
-    });
-    if (st) return st;
-    // 3. the fast pass's own s_true (same instruction sequence as its candidates)
-    TileArgs ta;
-    ta.q = w.q; ta.ent = m->entity_embedding; ta.modulus = m->modulus;
-    ta.nq = nq; ta.E = m->nentity; ta.Le = m->entity_dim; ta.K = K;
-    ta.c = a.c; ta.true_id = w.true_id; ta.s_true = w.s_true;
-    ta.fbits = w.bits; ta.W = a.W; ta.gt = w.gt; ta.win = win;
-    ta.qph = w.qph; ta.eph = w.eph;
-    auto tile_at = [&](int d) {
-      TileArgs x = ta;
-      const int64_t o = d * nq;
-      x.q += o * Le; x.true_id += o; x.s_true += o; x.fbits += o * W; x.gt += o; x.win = win_at(o);
-      if (x.qph) x.qph += o * 2 * (int64_t)K;
-      return x;
-    };
-    if (prot_tile) {
-      st = launch_status(launch_prot_phase(w.q, nqt, K, 0.f, 0, w.qph, s));
-      if (st) return st;
-    }
-    // s_true in the reference's order after the window (k_rank_true_ref):
-    // the split-bf16 path (instead of its gather pass), RotatE and pRotatE on
-    // the register tile (after its gather pass, whose fast s_true sizes the
-    // window's S; pRotatE: a point of the reference score's interval, the
-    // window widened by its width); the window then covers the candidate's
-    // error only
-    const bool true_ref = rp == RP_MFMA || (rp == RP_TILE && (m->model == KGE_ROTATE || prot_tile));
-    if (rp == RP_MFMA) {
-      // (q of both directions split in one launch: the tile is mode-independent)
-      st = launch_status(launch_split_bf16(w.q, nqt, m->entity_dim, w.qs, s));
-      if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
-      if (!st && !true_ref)
-        st = launch_status(launch_rank_mfma_x(1, w.qs, w.es, nqt, m->nentity, m->entity_dim, w.true_id, w.s_true,
-                                              w.bits, w.gt, win, s));
-    } else {
-      if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
-      if (rp == RP_MFMA32)
-        st = launch_status(launch_rank_mfma(1, w.q, m->entity_embedding, nqt, m->nentity, m->entity_dim, w.true_id,
-                                            w.s_true, w.bits, w.gt, win, s));
-      else if (rp == RP_TILE)
-        st = per_dir([&](int d, int md) { return launch_status(ops.rank_tile(md, 1, tile_at(d), s)); });
-    }
-    if (st) return st;
-    // 4. near-tie windows and the reference-order q
-    ra.true_exact = true_ref ? 1 : 0;
-    st = ref_stage(0);
-    if (st) return st;
-    if (true_ref) {
-      st = ref_stage(4);
-      if (st) return st;
-    }
-    // 5. fast counting pass: clear cases counted, near-ties listed (the MFMA
-    // tiles take both directions' queries in one launch)
-    g_rank_timer.mark(s, 1);  // (rank timer) 1: fast pass begins
-    if (rp == RP_MFMA) {
-      st = launch_status(launch_rank_mfma_x(0, w.qs, w.es, nqt, m->nentity, m->entity_dim, w.true_id, w.s_true,
-                                            w.bits, w.gt, win, s));
-    } else if (rp == RP_MFMA32) {
-      st = launch_status(launch_rank_mfma(0, w.q, m->entity_embedding, nqt, m->nentity, m->entity_dim, w.true_id,
-                                          w.s_true, w.bits, w.gt, win, s));
-    } else if (rp == RP_TILE) {
-      st = per_dir([&](int d, int md) { return launch_status(ops.rank_tile(md, 0, tile_at(d), s)); });
-    } else {
-      st = per_dir([&](int d, int md) {
-        RankArgs x = rank_at(d);
-        x.prep_only = 0;
-        x.zero_counts = 0;
-        return launch_status(ops.rank(md, geo.vec, geo.ns, x, s));
-      });
-    }
-    if (st) return st;
-    g_rank_timer.mark(s, 2);  // (rank timer) 2: fast pass ends
-    if (stage == RS_LIST) {  // the lists stay in the workspace for RS_ARGS / RS_FINISH
-      // pRotatE: every listed candidate's score as an interval under any
-      // library sin within one ulp, in the reference's order; those whose
-      // interval clears the true score's are decided now, only the rest go to
-      // the caller's sin.  Overflowed windows: the same over every candidate
-      // (k_rank_exact_iv).  KGE_RANK_SIN_SCREEN=0 (diagnostic): decide nothing.
-      RefArgs rs = ra;
-      rs.screen = 1;
-      rs.decide = env_int("KGE_RANK_SIN_SCREEN", 1) != 0 ? 1 : 0;
-      rs.ucnt_w = w.ucnt;
-      rs.ulist_w = w.ulist;
-      st = launch_status(ops.rank_ref(mode, 1, rs, s));
-      if (st) return st;
-      st = launch_status(ops.rank_ref(mode, 5, rs, s));
-      if (st) return st;
-      ea.ranks = nullptr;
-      ea.ties = nullptr;
-      ea.ltag = w.tag + 8;
-      return launch_status(launch_rank_emit(ea, s));
-    }
-  }
-  // 6. refinement in the reference's operation order; exact rescan on overflow
-  // (RS_FINISH: overflowed pRotatE windows were ranked by the list stage)
-  st = ref_stage(1);
+// The entity table's work (tag, statistics, split or phase table): it depends
+// on the table alone, and runs on ts — the caller's stream, or the side
+// stream's between rk_fork and rk_join (rank_fast).  The statistics and split
+// operands are reused only where the tag says this workspace already holds
+// them for this table (k_rank_tag).
+int rank_table(const RankRun& r, hipStream_t ts) {
+  const kge_model_desc* m = r.m;
+  const RankWs& w = r.w;
+  const int rp = r.rp;
+  const bool need_stats = (m->model == KGE_DISTMULT || m->model == KGE_COMPLEX || m->model == KGE_PROTATE);
+  // the derived table: split-bf16 operands (kind 1) or pRotatE's phase table
+  // (kind 2, tagged with its divisor's bits)
+  const float kappa = r.a.c.kappa_p;
+  int64_t kbits = 0;
+  memcpy(&kbits, &kappa, sizeof(kappa));
+  int st = launch_status(launch_rank_tag(w.tag, m->entity_embedding, m->nentity, m->entity_dim, r.reuse ? 1 : 0,
+                                         need_stats ? 1 : 0, rp == RP_MFMA ? 1 : (r.prot_tile ? 2 : 0),
+                                         r.prot_tile ? kbits : 0, ts));
   if (st) return st;
-  if (stage != RS_FINISH) {
-    st = ref_stage(2);
+  if (rp == RP_MFMA && need_stats) {  // (DistMult, ComplEx) one read of the table for both
+    st = launch_status(launch_split_stats(m->entity_embedding, m->nentity, m->entity_dim, w.es, w.stats, ts,
+                                          w.tag + 5, w.tag + 6));
+    if (st) return st;
+  } else {
+    if (need_stats) {
+      st = launch_status(launch_table_stats(m->entity_embedding, m->nentity, m->entity_dim, w.stats, ts, w.tag + 5));
+      if (st) return st;
+    }
+    if (rp == RP_MFMA) {
+      st = launch_status(launch_split_bf16(m->entity_embedding, m->nentity, m->entity_dim, w.es, ts, w.tag + 6));
+      if (st) return st;
+    }
+  }
+  if (r.prot_tile) {
+    st = launch_status(launch_prot_phase(m->entity_embedding, m->nentity, r.K, kappa, 1, w.eph, ts, w.tag + 6));
     if (st) return st;
   }
-  st = launch_status(launch_rank_emit(ea, s));
-  if (!st) g_rank_timer.mark(s, 3);  // (rank timer) 3: ranks written (the last of a call's marks counts)
+  return KGE_OK;
+}
+
+// The queries' work up to the fast pass, on the caller's stream (steps 1-5).
+// rsd: the side stream the table's work runs on, joined here before the first
+// launch that reads it, or null.
+int rank_queries(RankRun& r, Side* rsd) {
+  const kge_model_desc* m = r.m;
+  const RankWs& w = r.w;
+  const Geom& geo = r.geo;
+  const ModelOps& ops = *r.ops;
+  hipStream_t s = r.s;
+  const int rp = r.rp;
+  const int64_t nq = r.nq, nqt = r.nqt, W = r.W;
+  int st;
+  // 1. q, true ids (and, for the wave scan, s_true)
+  if (r.both && geo.ns != 0) {  // both directions' q in one launch (rows ≤ 2048 floats)
+    RankArgs x = r.a;
+    x.both_dirs = 1;
+    st = launch_status(ops.rank(KGE_HEAD_BATCH, geo.vec, geo.ns, x, s));
+  } else {
+    st = r.per_dir([&](int d, int md) { return launch_status(ops.rank(md, geo.vec, geo.ns, r.rank_at(d), s)); });
+  }
+  if (st) return st;
+  // 2. excluded candidates (filtered ids + the true id) as a bitmap (both
+  // directions in one launch where the row fits LDS)
+  st = r.both ? launch_filter_bits_both(r.queries, r.ftab ? 1 : 0, r.foff[0], r.fids[0], r.foff[1], r.fids[1],
+                                        w.true_id, nq, m->nentity, m->nrelation, w.bits, r.err, s)
+              : -1;
+  if (st > 0) return launch_status(st);
+  if (st < 0) st = r.per_dir([&](int d, int md) {
+    const int64_t o = d * nq;
+    if (r.ftab)
+      return launch_status(launch_filter_bits_tab(r.queries, md == KGE_HEAD_BATCH ? 1 : 0, r.foff[d], r.fids[d],
+                                                  w.true_id + o, nq, m->nentity, m->nrelation, w.bits + o * W,
+                                                  r.err, s));
+    return launch_status(launch_filter_bits(r.foff[d], r.fids[d], w.true_id + o, nq, m->nentity, w.bits + o * W,
+                                            r.err, s));
+  });
+  if (st) return st;
+  // 3. the fast pass's own s_true (same instruction sequence as its candidates)
+  TileArgs ta;
+  ta.q = w.q; ta.ent = m->entity_embedding; ta.modulus = m->modulus;
+  ta.nq = nq; ta.E = m->nentity; ta.Le = m->entity_dim; ta.K = r.K;
+  ta.c = r.a.c; ta.true_id = w.true_id; ta.s_true = w.s_true;
+  ta.fbits = w.bits; ta.W = W; ta.gt = w.gt; ta.win = r.win;
+  ta.qph = w.qph; ta.eph = w.eph;
+  auto tile_at = [&](int d) {
+    TileArgs x = ta;
+    const int64_t o = d * nq;
+    x.q += o * r.Le; x.true_id += o; x.s_true += o; x.fbits += o * W; x.gt += o; x.win = r.win_at(o);
+    if (x.qph) x.qph += o * 2 * (int64_t)r.K;
+    return x;
+  };
+  if (r.prot_tile) {
+    st = launch_status(launch_prot_phase(w.q, nqt, r.K, 0.f, 0, w.qph, s));
+    if (st) return st;
+  }
+  if (rp == RP_MFMA) {
+    // (q of both directions split in one launch: the tile is mode-independent)
+    st = launch_status(launch_split_bf16(w.q, nqt, m->entity_dim, w.qs, s));
+    if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
+    if (!st && !r.true_ref)
+      st = launch_status(launch_rank_mfma_x(1, w.qs, w.es, nqt, m->nentity, m->entity_dim, w.true_id, w.s_true,
+                                            w.bits, w.gt, r.win, s));
+  } else {
+    if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
+    if (rp == RP_MFMA32)
+      st = launch_status(launch_rank_mfma(1, w.q, m->entity_embedding, nqt, m->nentity, m->entity_dim, w.true_id,
+                                          w.s_true, w.bits, w.gt, r.win, s));
+    else if (rp == RP_TILE)
+      st = r.per_dir([&](int d, int md) { return launch_status(ops.rank_tile(md, 1, tile_at(d), s)); });
+  }
+  if (st) return st;
+  // 4. near-tie windows and the reference-order q
+  r.ra.true_exact = r.true_ref ? 1 : 0;
+  st = r.ref_stage(RefStage::Window);
+  if (st) return st;
+  if (r.true_ref) {
+    st = r.ref_stage(RefStage::TrueRef);
+    if (st) return st;
+  }
+  // 5. fast counting pass: clear cases counted, near-ties listed (the MFMA
+  // tiles take both directions' queries in one launch)
+  g_rank_timer.mark(s, 1);  // (rank timer) 1: fast pass begins
+  if (rp == RP_MFMA) {
+    st = launch_status(launch_rank_mfma_x(0, w.qs, w.es, nqt, m->nentity, m->entity_dim, w.true_id, w.s_true,
+                                          w.bits, w.gt, r.win, s));
+  } else if (rp == RP_MFMA32) {
+    st = launch_status(launch_rank_mfma(0, w.q, m->entity_embedding, nqt, m->nentity, m->entity_dim, w.true_id,
+                                        w.s_true, w.bits, w.gt, r.win, s));
+  } else if (rp == RP_TILE) {
+    st = r.per_dir([&](int d, int md) { return launch_status(ops.rank_tile(md, 0, tile_at(d), s)); });
+  } else {
+    st = r.per_dir([&](int d, int md) {
+      RankArgs x = r.rank_at(d);
+      x.prep_only = 0;
+      x.zero_counts = 0;
+      return launch_status(ops.rank(md, geo.vec, geo.ns, x, s));
+    });
+  }
+  if (st) return st;
+  g_rank_timer.mark(s, 2);  // (rank timer) 2: fast pass ends
+  return KGE_OK;
+}
+
+// Everything up to the near-tie lists (RS_ALL and RS_LIST).  KGE_RANK_SIDE=1
+// (diagnostic, same bits) runs the table's work on the side stream beside the
+// queries' q / bitmap / split (forked here, joined before the windows read the
+// statistics): measured 1-2 % SLOWER than one stream (a ~130 µs dispatch gap
+// before the counting tile after the cross-stream join; profiles/r06/rank), so
+// the default is the caller's stream, the table's work queued first.
+int rank_fast(RankRun& r) {
+  g_rank_timer.mark(r.s, 0, r.ndir);  // (rank timer) 0: the call starts
+  Side* rsd = env_int("KGE_RANK_SIDE", 0) != 0 ? side_for_device() : nullptr;
+  if (rsd) {
+    hipEventRecord(rsd->rk_fork, r.s);
+    hipStreamWaitEvent(rsd->s, rsd->rk_fork, 0);
+  }
+  int st = rank_table(r, rsd ? rsd->s : r.s);
+  if (st) return st;
+  if (rsd) hipEventRecord(rsd->rk_join, rsd->s);
+  return rank_queries(r, rsd);
+}
+
+// RS_LIST's tail: the lists stay in the workspace for RS_ARGS / RS_FINISH.
+// pRotatE: every listed candidate's score as an interval under any library sin
+// within one ulp, in the reference's order; those whose interval clears the
+// true score's are decided now, only the rest go to the caller's sin.
+// Overflowed windows: the same over every candidate (k_rank_exact_iv).
+// KGE_RANK_SIN_SCREEN=0 (diagnostic): decide nothing.
+int rank_list_tail(const RankRun& r) {
+  RefArgs rs = r.ra;
+  rs.screen = 1;
+  rs.decide = env_int("KGE_RANK_SIN_SCREEN", 1) != 0 ? 1 : 0;
+  rs.ucnt_w = r.w.ucnt;
+  rs.ulist_w = r.w.ulist;
+  int st = launch_status(r.ops->rank_ref(r.mode, RefStage::Refine, rs, r.s));
+  if (st) return st;
+  st = launch_status(r.ops->rank_ref(r.mode, RefStage::Interval, rs, r.s));
+  if (st) return st;
+  EmitArgs ea = r.ea;
+  ea.ranks = nullptr;
+  ea.ties = nullptr;
+  ea.ltag = r.w.tag + 8;
+  return launch_status(launch_rank_emit(ea, r.s));
+}
+
+// RS_ALL's and RS_FINISH's tail — 6. refinement in the reference's operation
+// order; exact rescan on overflow (RS_FINISH: overflowed pRotatE windows were
+// ranked by the list stage); the ranks
+int rank_refine_tail(const RankRun& r) {
+  int st = r.ref_stage(RefStage::Refine);
+  if (st) return st;
+  if (r.stage != RS_FINISH) {
+    st = r.ref_stage(RefStage::Exact);
+    if (st) return st;
+  }
+  st = launch_status(launch_rank_emit(r.ea, r.s));
+  if (!st) g_rank_timer.mark(r.s, 3);  // (rank timer) 3: ranks written (the last of a call's marks counts)
   return st;
 }
+
+int rank_impl(const RankCall& c) {
+  RankRun r;
+  int st = rank_validate(c, &r);
+  if (st || c.nq == 0) return st;
+  rank_bind(c, &r);
+  switch (c.stage) {
+    case RS_ARGS:
+      return launch_status(r.ops->rank_ref(c.mode, RefStage::SinArgs, r.ra, r.s));
+    case RS_FINISH:
+      return rank_refine_tail(r);
+    case RS_LIST:
+      st = rank_fast(r);
+      return st ? st : rank_list_tail(r);
+    case RS_ALL:
+      st = rank_fast(r);
+      return st ? st : rank_refine_tail(r);
+  }
+  return KGE_ERR_ARG;  // (not a RankStage)
+}
+
 }  // namespace
 }  // namespace kge
 
+using namespace kge;
+
 extern "C" {
+
+const char* kge_version(void) { return "knowledgegraphembedding_amd " KGE_ABI_VERSION " gfx950"; }
+
+const char* kge_status_string(int status) {
+  switch (status) {
+    case KGE_OK: return "ok";
+    case KGE_ERR_MODEL: return "model not supported";
+    case KGE_ERR_MODE: return "mode not supported";
+    case KGE_ERR_SHAPE: return "entity/relation dims inconsistent with the model";
+    case KGE_ERR_ARG: return "invalid argument";
+    case KGE_ERR_WORKSPACE: return "workspace too small";
+    case KGE_ERR_DIM: return "size outside the kernels' range (negatives per row, queries per call, LDS; wide rows under query shipping)";
+    case KGE_ERR_ABI: return "kge_model_desc.struct_size does not match this library (built against another kge_hip.h)";
+    default:
+      if (status >= KGE_ERR_HIP_BASE) return hipGetErrorString((hipError_t)(status - KGE_ERR_HIP_BASE));
+      return "unknown";
+  }
+}
+
+int kge_score(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
+              int64_t nneg, float* out, int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_SINGLE && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (batch == 0 && nneg >= 1) return KGE_OK;  // empty batch: nothing to score (buffers may be empty/NULL)
+  if (!pos || !out || !err_flag || batch < 0 || nneg < 1) return KGE_ERR_ARG;
+  Negatives cand;
+  st = negatives_of(mode, pos, neg, nneg, &cand);
+  if (st) return st;
+  ScoreArgs a;
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.pos = pos; a.neg = cand.ids; a.neg_stride = cand.stride;
+  a.B = batch; a.n = nneg; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = geo.eg; a.c = consts_of(m);
+  a.jpw = nneg < 16 ? nneg : 16;
+  a.out = out; a.err = err_flag;
+  const int64_t units = batch * ((nneg + a.jpw - 1) / a.jpw);
+  return launch_status(ops_for(m->model).score(kernel_mode(mode), geo.vec, geo.ns, a, units, as_stream(stream)));
+}
+
+size_t kge_backward_workspace_bytes(const kge_model_desc* m, int32_t mode, int64_t batch, int64_t nneg) {
+  (void)mode;
+  size_t b = 0;
+  carve_grad(nullptr, m, batch, nneg, &b);
+  return b;
+}
+
+int kge_score_backward(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
+                       int64_t nneg, const float* grad_scores, float* grad_entity, float* grad_relation,
+                       float* grad_modulus, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                       void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_SINGLE && mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!pos || !grad_scores || !grad_entity || !grad_relation || !err_flag || batch < 1 || nneg < 1)
+    return KGE_ERR_ARG;
+  if (!grad_streams_aligned(geo, grad_entity, grad_relation, nullptr)) return KGE_ERR_ARG;
+  Negatives cand;
+  st = negatives_of(mode, pos, neg, nneg, &cand);
+  if (st) return st;
+  size_t need = 0;
+  const GradWs w = carve_grad(workspace, m, batch, nneg, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+  StepCall c;  // the whole step, no loss terms, no optimizer
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.out = {grad_entity, grad_relation, grad_modulus};
+  const Batch b = batch_of(c, geo, cand, w);
+  RowArgs ra = row_args(b);
+  ra.op = ROW_GIVEN;
+  ra.g_in = grad_scores;
+  ra.n_lds = 0;
+  FinArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.B = batch;
+  fa.uni_weight = 1;
+  fa.uni_n = 1.f;
+  return run_grad(c, b, ra, fa);
+}
+
+size_t kge_train_workspace_bytes(const kge_model_desc* m, int64_t batch, int64_t nneg) {
+  size_t b = 0;
+  carve_grad(nullptr, m, batch, nneg, &b);
+  return b;
+}
+
+int kge_train_step(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
+                   int64_t nneg, const float* subsampling_weight, const float* weight_sum, int32_t uni_weight,
+                   int64_t uni_batch, int32_t adversarial, float adversarial_temperature, float regularization,
+                   const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
+                   float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  if (!adam) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  return train_impl(c);
+}
+
+int kge_train_step_grads(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                         int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
+                         int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
+                         float adversarial_temperature, float regularization, float* grad_entity,
+                         float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
+                         size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  return train_impl(c);
+}
+
+int kge_train_step_grads_phased(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                                int64_t batch, int64_t nneg, const float* subsampling_weight,
+                                const float* weight_sum, int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
+                                float adversarial_temperature, float regularization, float* grad_entity,
+                                float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
+                                size_t workspace_bytes, int32_t* err_flag, void* stream, int32_t phases,
+                                int64_t entity_begin, int64_t entity_end) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.phases = phases;
+  c.e_begin = entity_begin;
+  c.e_end = entity_end;
+  return train_impl(c);
+}
+
+int kge_train_rows_slice(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                         int64_t nrows, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
+                         int32_t uni_weight, int64_t uni_batch, int32_t adversarial, float adversarial_temperature,
+                         float* g_out, float* dq_out, float* stats_out, void* workspace, size_t workspace_bytes,
+                         int32_t* err_flag, void* stream) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, nrows, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature};
+  c.phases = KGE_PHASE_ROWS;
+  c.xstage = XS_ROWS_ONLY;
+  c.rows = {g_out, dq_out, stats_out};
+  return train_impl(c);
+}
+
+int kge_train_csr(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
+                  int64_t nneg, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.xstage = XS_CSR_ONLY;
+  return train_impl(c);
+}
+
+int kge_train_csr_range(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                        int64_t batch, int64_t nneg, int64_t entity_begin, int64_t entity_end, void* workspace,
+                        size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  if (!m || !entity_range_ok(m, entity_begin, entity_end)) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.xstage = XS_CSR_ONLY;
+  c.csr_lo = entity_begin;
+  c.csr_hi = entity_end;
+  return train_impl(c);
+}
+
+// The four kge_train_step_from_rows* entries: the step after the exchange, on
+// the gathered per-row factors (the row pass ran on the ranks).
+int kge_train_step_from_rows_phased(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                                    int64_t batch, int64_t nneg, const float* subsampling_weight,
+                                    const float* weight_sum, int32_t uni_weight, int64_t uni_batch,
+                                    float regularization, const float* g_in, const float* dq_in, float* stats_inout,
+                                    const kge_adam_desc* adam, float* grad_entity, float* grad_relation,
+                                    float* grad_modulus, float* losses_out, void* workspace, size_t workspace_bytes,
+                                    int32_t* err_flag, void* stream, int32_t phases, int64_t entity_begin,
+                                    int64_t entity_end, int32_t csr_ready, int32_t reg_relations) {
+  if (phases <= 0 || phases > KGE_PHASE_ALL) return KGE_ERR_ARG;
+  if (!entity_range_ok(m, entity_begin, entity_end)) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch};
+  c.loss.regularization = regularization;
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.phases = phases;
+  c.e_begin = entity_begin;
+  c.e_end = entity_end;
+  c.xstage = csr_ready ? XS_FROM_ROWS_CSR : XS_FROM_ROWS;
+  c.rows = {const_cast<float*>(g_in), const_cast<float*>(dq_in), stats_inout};
+  c.reg_relations = reg_relations ? 1 : 0;
+  return train_impl(c);
+}
+
+int kge_train_step_from_rows_range(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                                   int64_t batch, int64_t nneg, const float* subsampling_weight,
+                                   const float* weight_sum, int32_t uni_weight, int64_t uni_batch,
+                                   float regularization, const float* g_in, const float* dq_in, float* stats_inout,
+                                   const kge_adam_desc* adam, float* grad_entity, float* grad_relation,
+                                   float* grad_modulus, float* losses_out, void* workspace, size_t workspace_bytes,
+                                   int32_t* err_flag, void* stream, int64_t entity_begin, int64_t entity_end,
+                                   int32_t csr_ready, int32_t reg_relations) {
+  if (!entity_range_ok(m, entity_begin, entity_end)) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch};
+  c.loss.regularization = regularization;
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.e_begin = entity_begin;
+  c.e_end = entity_end;
+  c.xstage = csr_ready ? XS_FROM_ROWS_CSR : XS_FROM_ROWS;
+  c.rows = {const_cast<float*>(g_in), const_cast<float*>(dq_in), stats_inout};
+  c.reg_relations = reg_relations ? 1 : 0;
+  return train_impl(c);
+}
+
+int kge_train_step_from_rows(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                             int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
+                             int32_t uni_weight, int64_t uni_batch, float regularization, const float* g_in,
+                             const float* dq_in, float* stats_inout, const kge_adam_desc* adam, float* grad_entity,
+                             float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
+                             size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch};
+  c.loss.regularization = regularization;
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.xstage = XS_FROM_ROWS;
+  c.rows = {const_cast<float*>(g_in), const_cast<float*>(dq_in), stats_inout};
+  return train_impl(c);
+}
+
+int kge_train_step_from_rows_csr(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                                 int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
+                                 int32_t uni_weight, int64_t uni_batch, float regularization, const float* g_in,
+                                 const float* dq_in, float* stats_inout, const kge_adam_desc* adam, float* grad_entity,
+                                 float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
+                                 size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch};
+  c.loss.regularization = regularization;
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.xstage = XS_FROM_ROWS_CSR;
+  c.rows = {const_cast<float*>(g_in), const_cast<float*>(dq_in), stats_inout};
+  return train_impl(c);
+}
+
+int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh, int32_t stage,
+                  const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
+                  float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!sh || stage < KGE_SHIP_Q || stage > KGE_SHIP_ENTITY || !err_flag) return KGE_ERR_ARG;
+  const int64_t B = sh->batch, n = sh->nneg;
+  if (!sh->pos || !sh->neg || B < 1 || n < 1 || n > 8192) return KGE_ERR_ARG;
+  if (sh->world < 1 || sh->world > 4096 || sh->rank < 0 || sh->rank >= sh->world) return KGE_ERR_ARG;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
+  if (!sh->uni_weight && (!sh->subsampling_weight || !sh->weight_sum)) return KGE_ERR_ARG;
+  const bool head = (mode == KGE_HEAD_BATCH);
+  if (!sh->q || !sh->part || !sh->parts || !sh->scores || !sh->g || !sh->dq || !sh->pstats || !sh->ent_contrib ||
+      !sh->rel_contrib || !sh->row_stats || (head && (!sh->qp || !sh->pq)))
+    return KGE_ERR_ARG;
+  if (stage >= KGE_SHIP_CHAIN && !grad_relation) return KGE_ERR_ARG;
+  if (stage == KGE_SHIP_ENTITY && (!grad_entity || !losses_out || (m->model == KGE_PROTATE && !grad_modulus)))
+    return KGE_ERR_ARG;
+  if (adam && (!adam->entity.param || !adam->entity.exp_avg || !adam->entity.exp_avg_sq ||
+               adam->entity.param != m->entity_embedding))
+    return KGE_ERR_ARG;
+  if (!grad_streams_aligned(geo, grad_entity, grad_relation, adam)) return KGE_ERR_ARG;
+  size_t need = 0;
+  GradWs w = carve_grad(workspace, m, B, n, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+  // the shipped per-row buffers are the caller's (they cross the ranks between the stages)
+  w.q = sh->q; w.dq = sh->dq; w.g = sh->g;
+  w.ent_contrib = sh->ent_contrib; w.rel_contrib = sh->rel_contrib; w.row_stats = sh->row_stats;
+  hipStream_t s = as_stream(stream);
+  const ModelOps& op = ops_for(m->model);
+  const int kmode = kernel_mode(mode);
+  const Batch b = {m, geo, kmode, sh->pos, {sh->neg, n}, B, n, w, err_flag, s};
+  StepCall::Loss loss;
+  loss.subsampling_weight = sh->subsampling_weight;
+  loss.weight_sum = sh->weight_sum;
+  loss.uni_weight = sh->uni_weight;
+  loss.uni_batch = sh->uni_batch;
+
+  RowArgs ra = row_args(b);
+  ra.op = ROW_TRAIN;
+  ra.adversarial = sh->adversarial ? 1 : 0;
+  ra.adv_T = sh->adversarial_temperature;
+  ra.uni_weight = sh->uni_weight ? 1 : 0;
+  ra.uni_inv = 1.f / (float)(sh->uni_batch > 0 ? sh->uni_batch : B);
+  ra.sub_w = sh->subsampling_weight;
+  ra.w_sum = sh->weight_sum;
+  ra.n_lds = 0; ra.fuse_epi = 0;
+  ra.sh.own_lo = sh->own_begin; ra.sh.own_hi = sh->own_end;
+  ra.sh.world = sh->world; ra.sh.me = sh->rank;
+  ra.sh.q_in = sh->q; ra.sh.qp_in = sh->qp; ra.sh.qp_out = sh->qp;
+  ra.sh.part_out = sh->part; ra.sh.parts_in = sh->parts; ra.sh.s_out = sh->scores;
+  ra.sh.pq = sh->pq; ra.sh.pstats = sh->pstats;
+  Side* sd = side_for_device();
+  // this shard's entity rows; the relation table is replicated: its regulariser once, on rank 0
+  const EntRange own = {sh->own_begin, sh->own_end, entity_slices(geo, B, m->entity_dim), sh->rank == 0};
+  const float reg = sh->regularization;
+
+  switch (stage) {
+    case KGE_SHIP_Q:
+      return launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipQ, ra, 0, s));
+    case KGE_SHIP_ROWS: {
+      // the occurrence CSR of the global batch beside the row pass (it needs only the ids);
+      // only this shard's rows are visited by its entity pass
+      const CsrArgs ca = csr_args(b, sh->own_begin, sh->own_end);
+      hipStream_t ss = sd ? sd->s : s;
+      if (sd) {
+        hipEventRecord(sd->fork, s);
+        hipStreamWaitEvent(ss, sd->fork, 0);
+      }
+      st = launch_status(launch_csr(ca, ss));
+      if (st) return st;
+      if (sd) hipEventRecord(sd->csr_done, ss);
+      const size_t lds = row_lds(geo, m->entity_dim, ra, false);  // (wide rows: refused by the launch)
+      if (lds > LDS_MAX) return KGE_ERR_DIM;
+      return launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipRows, ra, lds, s));
+    }
+    case KGE_SHIP_MERGE:
+      return launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipMerge, ra, 0, s));
+    case KGE_SHIP_CHAIN:
+      st = launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipChain, ra, 0, s));
+      if (st) return st;
+      if (sd) hipStreamWaitEvent(s, sd->csr_done, 0);  // the relation pass reads the CSR
+      return launch_status(launch_rel_rows(
+          rel_args(b, own.reg_relations ? 3.f * reg : 0.f, m->nentity * own.per(), grad_relation, OPT_GRAD_ONLY), s));
+    case KGE_SHIP_ENTITY:
+      if (own.e_end > own.e_begin) {
+        const EntArgs ea = ent_args(b, own, sh->g, reg, grad_entity, opt_for(adam, adam ? &adam->entity : nullptr));
+        st = launch_status(op.entity(kmode, geo.vec, geo.ns, ea, s));
+        if (st) return st;
+      }
+      return launch_status(launch_finalize(
+          fin_args(fin_loss(loss, B, losses_out, err_flag), b, own, reg, grad_modulus, adam), s));
+  }
+  return KGE_ERR_ARG;  // (stage was checked above)
+}
+
+int kge_weight_sum(const float* w, int64_t n, float* out, void* stream) {
+  if (!w || !out || n < 0) return KGE_ERR_ARG;
+  return launch_status(launch_weight_sum(w, n, out, as_stream(stream)));
+}
+
+int kge_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, float beta1,
+                  float beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || numel < 0) return KGE_ERR_ARG;
+  if (numel == 0) return KGE_OK;
+  if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq)) return KGE_ERR_ARG;
+  return launch_status(launch_adam(param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, eps, step_size,
+                                   bias_correction2_sqrt, as_stream(stream)));
+}
+
+size_t kge_rank_workspace_bytes(const kge_model_desc* m, int64_t nq) {
+  size_t b = 0;
+  carve_rank(nullptr, m, nq, &b);
+  return b;
+}
 
 int kge_rank_filtered_ex(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq,
                          const int64_t* filt_off, const int64_t* filt_ids, int64_t* ranks_out, int32_t* ties_out,
                          int32_t* listed_out, int32_t path, void* workspace, size_t workspace_bytes,
                          int32_t* err_flag, void* stream) {
-  const int stage = (path & KGE_RANK_STAGE_LIST) ? RS_LIST : RS_ALL;
-  return rank_impl(m, mode, queries, nq, filt_off, filt_ids, ranks_out, ties_out, listed_out, path, workspace,
-                   workspace_bytes, err_flag, stream, stage, nullptr, nullptr, nullptr);
-}
-
-int kge_rank_filtered_both(const kge_model_desc* m, const int64_t* queries, int64_t nq,
-                           const int64_t* filt_off_head, const int64_t* filt_ids_head, const int64_t* filt_off_tail,
-                           const int64_t* filt_ids_tail, int64_t* ranks_out, int32_t* ties_out, int32_t* listed_out,
-                           int32_t path, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  if (path & KGE_RANK_STAGE_LIST) return KGE_ERR_ARG;  // pRotatE's three-call form is per direction
-  return rank_impl(m, KGE_HEAD_BATCH, queries, nq, filt_off_head, filt_ids_head, ranks_out, ties_out, listed_out,
-                   path, workspace, workspace_bytes, err_flag, stream, RS_ALL, nullptr, nullptr, nullptr,
-                   filt_off_tail, filt_ids_tail, 1);
-}
-
-int kge_selftest_sin(float range, int32_t* max_dist_out, void* stream) {
-  if (!max_dist_out) return KGE_ERR_ARG;
-  return launch_status(launch_selftest_sin(range, max_dist_out, as_stream(stream)));
-}
-
-int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,
-                      void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return rank_impl(m, mode, nullptr, nq, nullptr, nullptr, nullptr, nullptr, nullptr, RP_AUTO, workspace,
-                   workspace_bytes, err_flag, stream, RS_ARGS, item_off, nullptr, args_out);
-}
-
-int kge_rank_finish_sin(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off,
-                        const float* sin_values, int64_t* ranks_out, int32_t* ties_out, int32_t* listed_out,
-                        void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
-  return rank_impl(m, mode, nullptr, nq, nullptr, nullptr, ranks_out, ties_out, listed_out, RP_AUTO, workspace,
-                   workspace_bytes, err_flag, stream, RS_FINISH, item_off, sin_values, nullptr);
+  RankCall c = {m, nq, workspace, workspace_bytes, err_flag, stream};
+  c.stage = (path & KGE_RANK_STAGE_LIST) ? RS_LIST : RS_ALL;
+  c.mode = mode;
+  c.path = path;
+  c.queries = queries;
+  c.filt_off = filt_off;
+  c.filt_ids = filt_ids;
+  c.ranks_out = ranks_out;
+  c.ties_out = ties_out;
+  c.listed_out = listed_out;
+  return rank_impl(c);
 }
 
 int kge_rank_filtered(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq,
@@ -1405,22 +1727,69 @@ int kge_rank_filtered(const kge_model_desc* m, int32_t mode, const int64_t* quer
                               workspace, workspace_bytes, err_flag, stream);
 }
 
+int kge_rank_filtered_both(const kge_model_desc* m, const int64_t* queries, int64_t nq,
+                           const int64_t* filt_off_head, const int64_t* filt_ids_head, const int64_t* filt_off_tail,
+                           const int64_t* filt_ids_tail, int64_t* ranks_out, int32_t* ties_out, int32_t* listed_out,
+                           int32_t path, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  if (path & KGE_RANK_STAGE_LIST) return KGE_ERR_ARG;  // pRotatE's three-call form is per direction
+  RankCall c = {m, nq, workspace, workspace_bytes, err_flag, stream};
+  c.both = true;
+  c.path = path;
+  c.queries = queries;
+  c.filt_off = filt_off_head;
+  c.filt_ids = filt_ids_head;
+  c.filt_off_tail = filt_off_tail;
+  c.filt_ids_tail = filt_ids_tail;
+  c.ranks_out = ranks_out;
+  c.ties_out = ties_out;
+  c.listed_out = listed_out;
+  return rank_impl(c);
+}
+
+int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,
+                      void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  RankCall c = {m, nq, workspace, workspace_bytes, err_flag, stream};
+  c.stage = RS_ARGS;
+  c.mode = mode;
+  c.item_off = item_off;
+  c.args = args_out;
+  return rank_impl(c);
+}
+
+int kge_rank_finish_sin(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off,
+                        const float* sin_values, int64_t* ranks_out, int32_t* ties_out, int32_t* listed_out,
+                        void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  RankCall c = {m, nq, workspace, workspace_bytes, err_flag, stream};
+  c.stage = RS_FINISH;
+  c.mode = mode;
+  c.item_off = item_off;
+  c.sins = sin_values;
+  c.ranks_out = ranks_out;
+  c.ties_out = ties_out;
+  c.listed_out = listed_out;
+  return rank_impl(c);
+}
+
+int kge_selftest_sin(float range, int32_t* max_dist_out, void* stream) {
+  if (!max_dist_out) return KGE_ERR_ARG;
+  return launch_status(launch_selftest_sin(range, max_dist_out, as_stream(stream)));
+}
+
 int kge_stage_timer(int32_t command, float* stage_ms_out, int32_t n_out) {
-  constexpr int NS_ = KGE_TIMER_STAGES + 1;
   if (command == 0 || command == 1) {
     g_timer.on = (command == 1);
-    g_timer.used = 0;
+    g_timer.pool.used = 0;
     g_timer.seen = 0;
     g_timer.period = (command == 1 && n_out > 0) ? n_out : 1;
     if (command == 0) {
       g_rank_timer.on = false;
-      g_rank_timer.used = 0;
+      g_rank_timer.pool.used = 0;
     }
     return KGE_OK;
   }
   if (command == 4) {  // ranking calls: enable and reset
     g_rank_timer.on = true;
-    g_rank_timer.used = 0;
+    g_rank_timer.pool.used = 0;
     return KGE_OK;
   }
   if (command == 5) {  // ranking calls: summed stage times + the number of directions ranked
@@ -1428,15 +1797,17 @@ int kge_stage_timer(int32_t command, float* stage_ms_out, int32_t n_out) {
     if (!stage_ms_out || n_out < NR) return KGE_ERR_ARG;
     for (int k = 0; k < NR; ++k) stage_ms_out[k] = 0.f;
     const RankTimer& t = g_rank_timer;
+    const std::vector<hipEvent_t>& ev = t.pool.ev;
+    const size_t used = t.pool.used;
     size_t i = 0;
     int dirs = 0;
-    while (i < t.used) {
+    while (i < used) {
       if (t.slot[i] != 0) {  // (marks before the first call start: none are recorded so)
         ++i;
         continue;
       }
       size_t j = i + 1;
-      while (j < t.used && t.slot[j] != 0) ++j;
+      while (j < used && t.slot[j] != 0) ++j;
       // the call's marks [i, j): first and last event of each slot
       long first[NR], last[NR];
       for (int k = 0; k < NR; ++k) first[k] = last[k] = -1;
@@ -1447,12 +1818,12 @@ int kge_stage_timer(int32_t command, float* stage_ms_out, int32_t n_out) {
         last[sl] = (long)x;
       }
       if (last[NR - 1] >= 0) {  // the call wrote its ranks
-        hipError_t err = hipEventSynchronize(t.ev[last[NR - 1]]);
+        hipError_t err = hipEventSynchronize(ev[last[NR - 1]]);
         if (err != hipSuccess) return hip_status(err);
         for (int k = 0; k < KGE_RANK_TIMER_STAGES; ++k) {
           if (first[k] < 0 || last[k + 1] < 0) continue;
           float ms = 0.f;
-          err = hipEventElapsedTime(&ms, t.ev[first[k]], t.ev[last[k + 1]]);
+          err = hipEventElapsedTime(&ms, ev[first[k]], ev[last[k + 1]]);
           if (err != hipSuccess) return hip_status(err);
           stage_ms_out[k] += ms;
         }
@@ -1463,42 +1834,22 @@ int kge_stage_timer(int32_t command, float* stage_ms_out, int32_t n_out) {
     stage_ms_out[KGE_RANK_TIMER_STAGES] = (float)dirs;
     return KGE_OK;
   }
-  const size_t calls = g_timer.used / NS_;
-  if (command == 3) {
-    // per timed call: the 6 stage times, then the call's start relative to the
-    // first timed call's start (ms, device clock)
-    if (!stage_ms_out || (size_t)n_out < calls * NS_) return KGE_ERR_ARG;
-    for (size_t c = 0; c < calls; ++c) {
-      hipEvent_t* e = &g_timer.ev[c * NS_];
-      hipError_t err = hipEventSynchronize(e[NS_ - 1]);
-      if (err != hipSuccess) return hip_status(err);
-      for (int k = 0; k < KGE_TIMER_STAGES; ++k) {
-        float ms = 0.f;
-        err = hipEventElapsedTime(&ms, e[k], e[k + 1]);
-        if (err != hipSuccess) return hip_status(err);
-        stage_ms_out[c * NS_ + k] = ms;
-      }
-      float t0 = 0.f;
-      err = hipEventElapsedTime(&t0, g_timer.ev[0], e[0]);
-      if (err != hipSuccess) return hip_status(err);
-      stage_ms_out[c * NS_ + KGE_TIMER_STAGES] = t0;
-    }
-    return KGE_OK;
-  }
-  if (command != 2 || !stage_ms_out || n_out < NS_) return KGE_ERR_ARG;
-  for (int k = 0; k < NS_; ++k) stage_ms_out[k] = 0.f;
+  // training calls, TM_COUNT marks each — 2: the stage times summed over the
+  // timed calls, then their number; 3: per timed call, its stage times, then
+  // its start relative to the first timed call's start (ms, device clock)
+  if (command != 2 && command != 3) return KGE_ERR_ARG;
+  const bool per_call = (command == 3);
+  const hipEvent_t* ev = g_timer.pool.ev.data();
+  const size_t calls = g_timer.pool.used / TM_COUNT;
+  if (!stage_ms_out || (per_call ? (size_t)n_out < calls * TM_COUNT : n_out < TM_COUNT)) return KGE_ERR_ARG;
+  for (size_t k = 0; k < (per_call ? calls : 1) * TM_COUNT; ++k) stage_ms_out[k] = 0.f;
   for (size_t c = 0; c < calls; ++c) {
-    hipEvent_t* e = &g_timer.ev[c * NS_];
-    hipError_t err = hipEventSynchronize(e[NS_ - 1]);
+    float* ms = stage_ms_out + (per_call ? c * TM_COUNT : 0);
+    hipError_t err = add_stage_ms(ev + c * TM_COUNT, ms);
+    if (err == hipSuccess && per_call) err = hipEventElapsedTime(&ms[KGE_TIMER_STAGES], ev[0], ev[c * TM_COUNT]);
     if (err != hipSuccess) return hip_status(err);
-    for (int k = 0; k < KGE_TIMER_STAGES; ++k) {
-      float ms = 0.f;
-      err = hipEventElapsedTime(&ms, e[k], e[k + 1]);
-      if (err != hipSuccess) return hip_status(err);
-      stage_ms_out[k] += ms;
-    }
   }
-  stage_ms_out[KGE_TIMER_STAGES] = (float)calls;
+  if (!per_call) stage_ms_out[KGE_TIMER_STAGES] = (float)calls;
   return KGE_OK;
 }
 

@@ -294,15 +294,36 @@ struct TileArgs {
   const float* eph;        // pRotatE: [E, K, 2] (cos, sin) of the candidate phases
 };
 
+// What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
+enum class RowStage : int {
+  Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
+  Epilogue = 1,   // the separate epilogue (k_row_epi); nothing when fuse_epi
+  QOnly = 2,      // q build alone (the factor-exchange step rebuilds q for the global batch)
+  // query shipping (kge_ship_step; not for wide rows)
+  ShipQ = 3,      // q (and the positive's q, head-batch)
+  ShipRows = 4,   // the owned negatives' row pass
+  ShipMerge = 5,  // merge of the ranks' partial statistics
+  ShipChain = 6,  // chain rule
+};
+
+// What one ModelOps::rank_ref call launches (launch_rank_ref): the ranking's
+// reference-order refinement.
+enum class RefStage : int {
+  Window = 0,     // k_rank_window: each query's near-tie window δ and its reference-order q
+  Refine = 1,     // k_rank_refine: the listed candidates rescored in the reference's order
+  Exact = 2,      // k_rank_exact: queries whose window overflowed the list, over every candidate
+  SinArgs = 3,    // k_rank_sin_args: pRotatE phase sums of every item, for the caller's sin
+  TrueRef = 4,    // k_rank_true_ref: the true score in the reference's order (RefArgs.true_exact)
+  Interval = 5,   // k_rank_exact_iv: pRotatE's list stage, overflowed windows by score intervals
+};
+
 struct ModelOps {
   int (*score)(int mode, int vec, int ns, const ScoreArgs&, int64_t units, hipStream_t);
-  int (*row)(int mode, int vec, int ns, int stage, const RowArgs&, size_t lds, hipStream_t);
+  int (*row)(int mode, int vec, int ns, RowStage, const RowArgs&, size_t lds, hipStream_t);
   int (*entity)(int mode, int vec, int ns, const EntArgs&, hipStream_t);
   int (*rank)(int mode, int vec, int ns, const RankArgs&, hipStream_t);
   int (*rank_tile)(int mode, int gather, const TileArgs&, hipStream_t);
-  // stage 0: window (δ, reference q); 1: refine the listed candidates; 2: exact rescan of overflowed queries;
-  // 3: pRotatE phase sums of every item (k_rank_sin_args)
-  int (*rank_ref)(int mode, int stage, const RefArgs&, hipStream_t);
+  int (*rank_ref)(int mode, RefStage, const RefArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

@@ -2451,68 +2451,67 @@ __global__ __launch_bounds__(256) void k_rank_true_ref(RefArgs a) {
 }
 
 template <int M>
-int launch_rank_ref(int mode, int stage, const RefArgs& a, hipStream_t s) {
-  if (stage == 4) {
-    if (!a.s_true_w) return (int)hipErrorInvalidValue;
-    RefArgs b = a;
-    b.ref_global = refine_lp(a.Le) > 1024 ? 1 : 0;
-    const size_t lds = b.ref_global ? 0 : sizeof(float) * 16 * (size_t)refine_lp(a.Le);
-    const unsigned g4 = (unsigned)((a.nq + 7) / 8);
-    if (mode == BOTH_DIRS)
-      hipLaunchKernelGGL((k_rank_true_ref<M, BOTH_DIRS>), dim3(2 * g4), dim3(256), lds, s, b);
-    else if (mode == HEAD_BATCH)
-      hipLaunchKernelGGL((k_rank_true_ref<M, HEAD_BATCH>), dim3(g4), dim3(256), lds, s, b);
-    else
-      hipLaunchKernelGGL((k_rank_true_ref<M, TAIL_BATCH>), dim3(g4), dim3(256), lds, s, b);
-    return (int)hipGetLastError();
-  }
-  if (stage == 3) {
-    if (M != PROTATE) return (int)hipErrorInvalidValue;
-    if (mode == HEAD_BATCH)
-      hipLaunchKernelGGL((k_rank_sin_args<M, HEAD_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_rank_sin_args<M, TAIL_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-  }
-  if (stage == 5) {
-    if (M != PROTATE) return (int)hipErrorInvalidValue;
-    const unsigned g5 = (unsigned)((a.nq + 3) / 4);
-    if (mode == HEAD_BATCH)
-      hipLaunchKernelGGL((k_rank_exact_iv<M, HEAD_BATCH>), dim3(g5), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_rank_exact_iv<M, TAIL_BATCH>), dim3(g5), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-  }
-  const unsigned g = (unsigned)(stage == 1 ? a.nq : (a.nq + 3) / 4);  // refine: a block per query
+int launch_rank_ref(int mode, RefStage stage, const RefArgs& a, hipStream_t s) {
   RefArgs b = a;
   size_t lds = 0;
-  if (stage == 1) {
-    // q and one row slot must fit the 64 KB of LDS; wider rows are read in place
-    b.ref_global = (refine_lp(a.Le) * 2 + refine_capp(a.cap) > 65536 / 4) ? 1 : 0;
-    b.ref_slots = b.ref_global ? 8 : refine_slots(a.Le, a.cap);
-    lds = sizeof(float) * (size_t)(b.ref_global ? refine_capp(a.cap)
-                                                : refine_lp(a.Le) * (1 + b.ref_slots) + refine_capp(a.cap));
-  }
+  unsigned g = (unsigned)((a.nq + 3) / 4);
   // (BOTH_DIRS: both directions' queries in one launch, twice the grid)
   auto go = [&](auto kh, auto kt, auto kb) {
     if (mode == BOTH_DIRS) hipLaunchKernelGGL(kb, dim3(2 * g), dim3(256), lds, s, b);
     else hipLaunchKernelGGL(mode == HEAD_BATCH ? kh : kt, dim3(g), dim3(256), lds, s, b);
     return (int)hipGetLastError();
   };
-  if (stage == 0)
-    return go(k_rank_window<M, HEAD_BATCH>, k_rank_window<M, TAIL_BATCH>, k_rank_window<M, BOTH_DIRS>);
-  if (stage == 1) {
-    const int n4 = a.Le >> 2;  // float4 per row (the prefetch path's condition is rechecked in the kernel)
-    if (n4 <= 128)
-      return go(k_rank_refine<M, HEAD_BATCH, 4>, k_rank_refine<M, TAIL_BATCH, 4>, k_rank_refine<M, BOTH_DIRS, 4>);
-    if (n4 <= 256)
-      return go(k_rank_refine<M, HEAD_BATCH, 8>, k_rank_refine<M, TAIL_BATCH, 8>, k_rank_refine<M, BOTH_DIRS, 8>);
-    if (n4 <= 512)
-      return go(k_rank_refine<M, HEAD_BATCH, 16>, k_rank_refine<M, TAIL_BATCH, 16>,
-                k_rank_refine<M, BOTH_DIRS, 16>);
-    return go(k_rank_refine<M, HEAD_BATCH, 0>, k_rank_refine<M, TAIL_BATCH, 0>, k_rank_refine<M, BOTH_DIRS, 0>);
+  switch (stage) {
+    case RefStage::TrueRef: {
+      if (!a.s_true_w) return (int)hipErrorInvalidValue;
+      b.ref_global = refine_lp(a.Le) > 1024 ? 1 : 0;
+      lds = b.ref_global ? 0 : sizeof(float) * 16 * (size_t)refine_lp(a.Le);
+      const unsigned g4 = (unsigned)((a.nq + 7) / 8);
+      if (mode == BOTH_DIRS)
+        hipLaunchKernelGGL((k_rank_true_ref<M, BOTH_DIRS>), dim3(2 * g4), dim3(256), lds, s, b);
+      else if (mode == HEAD_BATCH)
+        hipLaunchKernelGGL((k_rank_true_ref<M, HEAD_BATCH>), dim3(g4), dim3(256), lds, s, b);
+      else
+        hipLaunchKernelGGL((k_rank_true_ref<M, TAIL_BATCH>), dim3(g4), dim3(256), lds, s, b);
+      return (int)hipGetLastError();
+    }
+    case RefStage::SinArgs:
+      if (M != PROTATE) return (int)hipErrorInvalidValue;
+      if (mode == HEAD_BATCH)
+        hipLaunchKernelGGL((k_rank_sin_args<M, HEAD_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((k_rank_sin_args<M, TAIL_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    case RefStage::Interval:
+      if (M != PROTATE) return (int)hipErrorInvalidValue;
+      if (mode == HEAD_BATCH)
+        hipLaunchKernelGGL((k_rank_exact_iv<M, HEAD_BATCH>), dim3(g), dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((k_rank_exact_iv<M, TAIL_BATCH>), dim3(g), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    case RefStage::Window:
+      return go(k_rank_window<M, HEAD_BATCH>, k_rank_window<M, TAIL_BATCH>, k_rank_window<M, BOTH_DIRS>);
+    case RefStage::Refine: {
+      g = (unsigned)a.nq;  // a block per query
+      // q and one row slot must fit the 64 KB of LDS; wider rows are read in place
+      b.ref_global = (refine_lp(a.Le) * 2 + refine_capp(a.cap) > 65536 / 4) ? 1 : 0;
+      b.ref_slots = b.ref_global ? 8 : refine_slots(a.Le, a.cap);
+      lds = sizeof(float) * (size_t)(b.ref_global ? refine_capp(a.cap)
+                                                  : refine_lp(a.Le) * (1 + b.ref_slots) + refine_capp(a.cap));
+      const int n4 = a.Le >> 2;  // float4 per row (the prefetch path's condition is rechecked in the kernel)
+      if (n4 <= 128)
+        return go(k_rank_refine<M, HEAD_BATCH, 4>, k_rank_refine<M, TAIL_BATCH, 4>, k_rank_refine<M, BOTH_DIRS, 4>);
+      if (n4 <= 256)
+        return go(k_rank_refine<M, HEAD_BATCH, 8>, k_rank_refine<M, TAIL_BATCH, 8>, k_rank_refine<M, BOTH_DIRS, 8>);
+      if (n4 <= 512)
+        return go(k_rank_refine<M, HEAD_BATCH, 16>, k_rank_refine<M, TAIL_BATCH, 16>,
+                  k_rank_refine<M, BOTH_DIRS, 16>);
+      return go(k_rank_refine<M, HEAD_BATCH, 0>, k_rank_refine<M, TAIL_BATCH, 0>, k_rank_refine<M, BOTH_DIRS, 0>);
+    }
+    case RefStage::Exact:
+      return go(k_rank_exact<M, HEAD_BATCH>, k_rank_exact<M, TAIL_BATCH>, k_rank_exact<M, BOTH_DIRS>);
   }
-  return go(k_rank_exact<M, HEAD_BATCH>, k_rank_exact<M, TAIL_BATCH>, k_rank_exact<M, BOTH_DIRS>);
+  return -1;  // (not a RefStage)
 }
 
 // ------------------------------------------------------------ dispatch
@@ -2523,36 +2522,38 @@ struct Launch {
     hipLaunchKernelGGL((k_score<M, MODE, VEC, NS>), dim3(grid), dim3(256), 0, s, a);
     return (int)hipGetLastError();
   }
-  // stage 0: q build + gather loop (+ the epilogue in its tail when fuse_epi;
-  // launched first: the GPU starts on the big kernel while the host issues the
-  // rest); stage 1: the separate epilogue (k_row_epi) when not fused; stage 2:
-  // q build alone (the factor-exchange step rebuilds q for the global batch)
-  static int row(int stage, const RowArgs& a, size_t lds, hipStream_t s) {
-    if (stage >= 3) {  // query shipping: 3 q, 4 owned negatives, 5 merge, 6 chain rule
-      if (stage == 3)
-        hipLaunchKernelGGL((k_ship_q<M, MODE, VEC, NS>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, s, a);
-      else if (stage == 4)
-        hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, false, true>), dim3((unsigned)a.B), dim3(256), lds, s, a);
-      else if (stage == 5)
-        hipLaunchKernelGGL((k_ship_merge<M, MODE, VEC, NS>), dim3((unsigned)a.B), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_ship_chain<M, MODE, VEC, NS>), dim3((unsigned)a.B), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
+  // (RowStage::Pass is launched first: the GPU starts on the big kernel while
+  // the host issues the rest)
+  static int row(RowStage stage, const RowArgs& a, size_t lds, hipStream_t s) {
+    const dim3 rows((unsigned)a.B), quads((unsigned)((a.B + 3) / 4));
+    switch (stage) {
+      case RowStage::ShipQ:
+        hipLaunchKernelGGL((k_ship_q<M, MODE, VEC, NS>), quads, dim3(256), 0, s, a);
+        break;
+      case RowStage::ShipRows:
+        hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, false, true>), rows, dim3(256), lds, s, a);
+        break;
+      case RowStage::ShipMerge:
+        hipLaunchKernelGGL((k_ship_merge<M, MODE, VEC, NS>), rows, dim3(256), 0, s, a);
+        break;
+      case RowStage::ShipChain:
+        hipLaunchKernelGGL((k_ship_chain<M, MODE, VEC, NS>), rows, dim3(256), 0, s, a);
+        break;
+      case RowStage::QOnly:
+        hipLaunchKernelGGL((k_build_q<M, MODE, VEC, NS>), quads, dim3(256), 0, s, a);
+        break;
+      case RowStage::Epilogue:
+        if (a.fuse_epi) return 0;  // done in k_row's tail
+        hipLaunchKernelGGL((k_row_epi<M, MODE, VEC, NS>), rows, dim3(256), 0, s, a);
+        break;
+      case RowStage::Pass:
+        if (a.timer_mid) a.timer_mid(s);
+        if (a.fuse_epi)
+          hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, true>), rows, dim3(256), lds, s, a);
+        else
+          hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, false>), rows, dim3(256), lds, s, a);
+        break;
     }
-    if (stage == 2) {
-      hipLaunchKernelGGL((k_build_q<M, MODE, VEC, NS>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
-    }
-    if (stage == 1) {
-      if (a.fuse_epi) return 0;  // done in k_row's tail
-      hipLaunchKernelGGL((k_row_epi<M, MODE, VEC, NS>), dim3((unsigned)a.B), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
-    }
-    if (a.timer_mid) a.timer_mid(s);
-    if (a.fuse_epi)
-      hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, true>), dim3((unsigned)a.B), dim3(256), lds, s, a);
-    else
-      hipLaunchKernelGGL((k_row<M, MODE, VEC, NS, false>), dim3((unsigned)a.B), dim3(256), lds, s, a);
     return (int)hipGetLastError();
   }
   // column-sliced pass for float4 rows; the row-per-wave pass otherwise
@@ -2629,7 +2630,7 @@ int dispatch(int mode, int vec, int ns, Args&&... args) {
 template <int M, int MODE, int VEC, int NS>
 struct RunScore { static int run(const ScoreArgs& a, int64_t u, hipStream_t s) { return Launch<M, MODE, VEC, NS>::score(a, u, s); } };
 template <int M, int MODE, int VEC, int NS>
-struct RunRow { static int run(int stage, const RowArgs& a, size_t l, hipStream_t s) { return Launch<M, MODE, VEC, NS>::row(stage, a, l, s); } };
+struct RunRow { static int run(RowStage stage, const RowArgs& a, size_t l, hipStream_t s) { return Launch<M, MODE, VEC, NS>::row(stage, a, l, s); } };
 template <int M, int MODE, int VEC, int NS>
 struct RunEntity { static int run(const EntArgs& a, hipStream_t s) { return Launch<M, MODE, VEC, NS>::entity(a, s); } };
 template <int M, int MODE, int VEC, int NS>
@@ -2640,7 +2641,7 @@ struct ModelTable {
   static int score(int mode, int vec, int ns, const ScoreArgs& a, int64_t u, hipStream_t s) {
     return dispatch<M, RunScore>(mode, vec, ns, a, u, s);
   }
-  static int row(int mode, int vec, int ns, int stage, const RowArgs& a, size_t l, hipStream_t s) {
+  static int row(int mode, int vec, int ns, RowStage stage, const RowArgs& a, size_t l, hipStream_t s) {
     return dispatch<M, RunRow>(mode, vec, ns, stage, a, l, s);
   }
   static int entity(int mode, int vec, int ns, const EntArgs& a, hipStream_t s) {

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void k_rank_emit(EmitArgs a) {
 //   the three chained MFMAs  ≤ 32·u each on partial sums ≤ (1 + 2^-8)^2 (1 + 2^-7)·P_slab
 //                            (2u per internal add, any order)      →  97.6·u·P
 //   the running sum          1.02·nslab·u·P
-// → fast_u = (98.8 + 1.02·nslab)·u·P plus the split term (kge_capi.hip rank_impl,
+// → fast_u = (98.8 + 1.02·nslab)·u·P plus the split term (kge_capi.hip rank_bind,
 // RefArgs.fast_u; the window k_rank_window sizes from both), against the fp32 tile's K·u.
 //
 // Operands are split once per call into a tile-linear layout

@@ -466,21 +466,25 @@ struct Launch<M, MODE, 1, 0> {
     hipLaunchKernelGGL((k_score_w<M, MODE>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);
     return (int)hipGetLastError();
   }
-  // stage 0: the row pass (+ its epilogue when fuse_epi); 1: the separate
-  // epilogue; 2: q alone; query-shipping stages: not for wide rows
-  static int row(int stage, const RowArgs& a, size_t lds, hipStream_t s) {
-    if (stage >= 3) return -1;
-    if (stage == 2) {
-      hipLaunchKernelGGL((k_build_q_w<M, MODE>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
+  static int row(RowStage stage, const RowArgs& a, size_t lds, hipStream_t s) {
+    switch (stage) {
+      case RowStage::ShipQ:
+      case RowStage::ShipRows:
+      case RowStage::ShipMerge:
+      case RowStage::ShipChain:
+        return -1;  // query shipping: not for wide rows
+      case RowStage::QOnly:
+        hipLaunchKernelGGL((k_build_q_w<M, MODE>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, s, a);
+        break;
+      case RowStage::Epilogue:
+        if (a.fuse_epi) return 0;
+        hipLaunchKernelGGL((k_row_epi<M, MODE, 1, 0>), dim3((unsigned)a.B), dim3(256), 0, s, a);
+        break;
+      case RowStage::Pass:
+        if (a.timer_mid) a.timer_mid(s);
+        hipLaunchKernelGGL((k_row_w<M, MODE>), dim3((unsigned)a.B), dim3(256), lds, s, a);
+        break;
     }
-    if (stage == 1) {
-      if (a.fuse_epi) return 0;
-      hipLaunchKernelGGL((k_row_epi<M, MODE, 1, 0>), dim3((unsigned)a.B), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
-    }
-    if (a.timer_mid) a.timer_mid(s);
-    hipLaunchKernelGGL((k_row_w<M, MODE>), dim3((unsigned)a.B), dim3(256), lds, s, a);
     return (int)hipGetLastError();
   }
   static int entity(const EntArgs& a, hipStream_t s) {

@@ -76,6 +76,14 @@ _STATES: dict = {}
 _WS_BYTES: dict = {}  # (dims, counts, B, n) -> kge_train_workspace_bytes
 
 
+def _train_ws_bytes(desc: _lib.ModelDesc, B: int, n: int) -> int:
+    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n)
+    need = _WS_BYTES.get(key)
+    if need is None:
+        need = _WS_BYTES[key] = _lib.load().kge_train_workspace_bytes(desc, B, n)
+    return need
+
+
 def state(dev: torch.device) -> _DeviceState:
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     st = _STATES.get(key)
@@ -212,12 +220,8 @@ def train_step_grads(desc: _lib.ModelDesc, mode: str, pos: torch.Tensor, neg: to
     w = sub_w.to(dev, dtype=torch.float32, non_blocking=True).contiguous().view(-1)
     B, n = neg.shape
     lib = _lib.load()
-    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n)
-    need = _WS_BYTES.get(key)
-    if need is None:
-        need = _WS_BYTES[key] = lib.kge_train_workspace_bytes(desc, B, n)
     st = state(dev)
-    ws = st.workspace(need)
+    ws = st.workspace(_train_ws_bytes(desc, B, n))
     common = (desc, _lib.MODE_IDS[mode], pos.data_ptr(), neg.data_ptr(), B, n, w.data_ptr(), _ptr(weight_sum_dev),
               int(bool(uni_weight)), int(uni_batch), int(bool(adversarial)), float(temperature), float(regularization))
     tail = (grad_entity.data_ptr(), grad_relation.data_ptr(), _ptr(grad_modulus), losses.data_ptr(), ws.data_ptr(),
@@ -235,12 +239,7 @@ def train_step_grads(desc: _lib.ModelDesc, mode: str, pos: torch.Tensor, neg: to
 
 
 def _train_ws(desc: _lib.ModelDesc, B: int, n: int, dev) -> torch.Tensor:
-    lib = _lib.load()
-    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n)
-    need = _WS_BYTES.get(key)
-    if need is None:
-        need = _WS_BYTES[key] = lib.kge_train_workspace_bytes(desc, B, n)
-    return state(dev).workspace(need)
+    return state(dev).workspace(_train_ws_bytes(desc, B, n))
 
 
 _AUX_WS: dict = {}
@@ -251,11 +250,7 @@ def exchange_workspace(desc: _lib.ModelDesc, B: int, n: int, dev) -> torch.Tenso
     train_csr runs on a side stream while this rank's row pass (which uses the
     shared per-device workspace) is still running, so the two must not share
     memory.  Grown (after a device sync) only when a larger batch comes."""
-    lib = _lib.load()
-    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n)
-    need = _WS_BYTES.get(key)
-    if need is None:
-        need = _WS_BYTES[key] = lib.kge_train_workspace_bytes(desc, B, n)
+    need = _train_ws_bytes(desc, B, n)
     t = _AUX_WS.get(dev)
     if t is None or t.numel() < need:
         if t is not None:

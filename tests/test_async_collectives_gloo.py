@@ -22,7 +22,7 @@ consecutive steps with different data and no extra host synchronisation:
     replica must hold every rank's rows of THAT step.
 
 The C-ABI's own side stream (CSR, relation pass) is joined by events inside
-each call (kge_capi.hip run_grad), so no collective ever sees it."""
+each call (kge_capi.hip entity_phase / finalize_phase), so no collective ever sees it."""
 import os
 import socket
 from argparse import Namespace
