@@ -490,6 +490,55 @@ int kge_rank_filtered_both(const kge_model_desc *m, const int64_t *queries, int6
                            size_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /*
+ * Top-k link prediction — "given (h, r), which tails score highest?" (the
+ * reference has no such method: its users call KGEModel.forward with every
+ * entity as a negative, model.py:72-164, and torch.topk the [nq, E] scores).
+ *   queries [nq,3] (h,r,t); KGE_TAIL_BATCH predicts tails from (h, r),
+ *   KGE_HEAD_BATCH heads from (r, t).  The predicted column is never read and
+ *   never range-checked (callers may pass -1).  An out-of-range id in one of
+ *   the other two columns sets KGE_DEVERR_INDEX and fills that query's outputs
+ *   with id -1 and score NaN; the other queries proceed.
+ *   filt_off / filt_ids: the candidates to exclude, in the two forms of
+ *   kge_rank_filtered_ex — per-query lists, or with path | KGE_RANK_FILTER_TABLE
+ *   the whole filter index; filt_off == NULL: no filter.  There is no "true
+ *   id": nothing is excluded beyond the lists.
+ *   ids_out [nq,k] int64, scores_out [nq,k] fp32: each query's k best
+ *   unexcluded candidates ordered by (score descending, id ascending) — a total
+ *   order, so the result is deterministic and does not depend on `parts`, on
+ *   the launch geometry or on which other queries share the call.  If fewer
+ *   than k candidates remain, the tail is padded with id -1 and score -inf.  A
+ *   candidate whose score is NaN (or -inf, which the padding means) is never
+ *   selected.
+ * "score" is the fast pass's own fp32 score — the per-element arithmetic of the
+ * ranking's fast pass, with device cos / sin for RotatE (relation_trig is not
+ * read).  UNLIKE the ranks of kge_rank_filtered*, which are the reference's bit
+ * for bit, these scores agree with the reference to the score tolerance
+ * (1e-4 * max(|s|, 1), as kge_score), so candidates whose reference scores lie
+ * closer than that may come out in the other order.
+ *   path low bits: 0 auto, 2 register tile, 3 wave scan, with the eligibility
+ *   rules of kge_rank_filtered_ex (2 for rows the tile cannot take:
+ *   KGE_ERR_ARG).  The MFMA paths 1 and 4 have no top-k form: KGE_ERR_ARG.
+ *   The two paths may differ in the last bits of a score; each alone is
+ *   deterministic.  Rows over 2048 floats per (half-)row: KGE_ERR_DIM.
+ *   parts: the number of candidate ranges the table is cut into (at most 64,
+ *   and at most one per 64 candidates); 0 = chosen so that the grid fills the
+ *   device when nq is small.  Each (query block, part) produces a partial
+ *   list; a merge kernel reduces them.
+ * Host checks, in this order: the model (as every entry), mode, then null
+ * queries / ids_out / scores_out / err_flag, nq < 0, parts < 0 or a bad path
+ * (KGE_ERR_ARG); nq == 0 returns KGE_OK; k < 1 or k > KGE_TOPK_MAX_K and
+ * nq > 65535 (KGE_ERR_DIM); the path's fit; the workspace (KGE_ERR_WORKSPACE).
+ * The workspace holds the q vectors, the bitmap, pRotatE's phase tables and the
+ * [nq, parts, k] partial lists — never an [nq, E] score matrix.
+ */
+#define KGE_TOPK_MAX_K 128
+size_t kge_topk_workspace_bytes(const kge_model_desc *m, int64_t nq, int32_t k, int32_t parts);
+int kge_topk(const kge_model_desc *m, int32_t mode, const int64_t *queries, int64_t nq,
+             const int64_t *filt_off, const int64_t *filt_ids, int32_t k, int64_t *ids_out,
+             float *scores_out, int32_t path, int32_t parts, void *workspace, size_t workspace_bytes,
+             int32_t *err_flag, void *stream);
+
+/*
  * pRotatE ranks bit-exact to the reference — whose sin (model.py:245) is its
  * CPU vector library's (ATen → MKL VML here), which no device instruction
  * sequence reproduces — in three calls on one stream and workspace:

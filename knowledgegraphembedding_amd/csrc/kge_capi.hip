@@ -1319,6 +1319,122 @@ int rank_impl(const RankCall& c) {
   return KGE_ERR_ARG;  // (not a RankStage)
 }
 
+// =================================================================== top-k
+
+// The candidate parts of a top-k call: `parts` as asked (0: enough workgroups
+// to fill the device's 256 CUs twice when the query blocks alone do not), at
+// most 64 (a lane of the merge wave per part) and one per 64-candidate tile;
+// span = candidates per part, a multiple of 64.
+int topk_parts(const kge_model_desc* m, int64_t nq, int32_t parts, int64_t* span) {
+  const int64_t tiles = (m->nentity + 63) / 64, qblocks = (nq + 63) / 64;
+  int64_t p = parts > 0 ? parts : (512 + qblocks - 1) / (qblocks > 0 ? qblocks : 1);
+  if (p > 64) p = 64;
+  if (p > tiles) p = tiles;
+  if (p < 1) p = 1;
+  const int64_t tpp = (tiles + p - 1) / p;  // tiles per part
+  *span = tpp * 64;
+  return (int)((tiles + tpp - 1) / tpp);    // (no empty part)
+}
+
+struct TopkWs {
+  float *q, *qph, *eph, *pscore;
+  int64_t *qsan, *state;
+  uint32_t* bits;
+  int32_t* pid;
+};
+TopkWs carve_topk(void* ws, const kge_model_desc* m, int64_t nq, int k, int parts, size_t* bytes) {
+  Carver c(ws);
+  TopkWs w;
+  const bool ph = m->model == KGE_PROTATE && rank_path(m, RP_TILE) == RP_TILE;
+  w.eph = c.take<float>(ph ? 2 * m->nentity * (int64_t)m->entity_dim : 0);
+  w.qph = c.take<float>(ph ? 2 * nq * (int64_t)m->entity_dim : 0);
+  w.q = c.take<float>(nq * (int64_t)m->entity_dim);
+  w.qsan = c.take<int64_t>(3 * nq);
+  w.state = c.take<int64_t>(nq);
+  w.bits = c.take<uint32_t>(nq * ((m->nentity + 31) / 32));
+  w.pscore = c.take<float>(nq * (int64_t)parts * k);
+  w.pid = c.take<int32_t>(nq * (int64_t)parts * k);
+  *bytes = c.off + 256;
+  return w;
+}
+
+int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq, const int64_t* filt_off,
+              const int64_t* filt_ids, int32_t k, int64_t* ids_out, float* scores_out, int32_t path_flags,
+              int32_t parts_req, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!queries || !ids_out || !scores_out || !err_flag || nq < 0 || parts_req < 0) return KGE_ERR_ARG;
+  if (path_flags & ~(7 | KGE_RANK_FILTER_TABLE)) return KGE_ERR_ARG;
+  const bool ftab = (path_flags & KGE_RANK_FILTER_TABLE) != 0;
+  const int path = path_flags & 7;
+  if (path != RP_AUTO && path != RP_TILE && path != RP_SCAN) return KGE_ERR_ARG;  // (no MFMA top-k)
+  if (filt_off && !filt_ids) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  if (k < 1 || k > KGE_TOPK_MAX_K) return KGE_ERR_DIM;
+  if (nq > 65535) return KGE_ERR_DIM;  // the bitmap launch puts queries on grid.y
+  if (geo.ns == 0) return KGE_ERR_DIM;  // rows over 2048 floats: not served
+  const bool tile_ok = rank_path(m, RP_TILE) == RP_TILE;
+  if (path == RP_TILE && !tile_ok) return KGE_ERR_ARG;
+  const bool tile = (path == RP_SCAN) ? false : tile_ok;
+  int64_t span = 0;
+  const int parts = topk_parts(m, nq, parts_req, &span);
+  size_t need = 0;
+  const TopkWs w = carve_topk(workspace, m, nq, k, parts, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  const ModelOps& ops = ops_for(m->model);
+  hipStream_t s = as_stream(stream);
+  const int md = kernel_mode(mode);
+  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
+  const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
+  const int64_t W = (m->nentity + 31) / 32;
+  TopkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.queries = queries; a.nq = nq; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = geo.eg; a.c = consts_of(m);
+  a.q = w.q; a.qsan = w.qsan; a.state = w.state; a.fbits = w.bits; a.W = W;
+  a.k = k; a.parts = parts; a.span = span; a.pscore = w.pscore; a.pid = w.pid; a.err = err_flag;
+  // 1. q and each query's state
+  a.stage = 0;
+  st = launch_status(ops.topk(md, geo.vec, geo.ns, a, s));
+  if (st) return st;
+  // 2. the excluded candidates as a bitmap (state stands in for the true id: negative, no bit)
+  if (!filt_off)
+    st = hip_status(hipMemsetAsync(w.bits, 0, (size_t)nq * W * sizeof(uint32_t), s));
+  else if (ftab)
+    st = launch_status(launch_filter_bits_tab(w.qsan, mode == KGE_HEAD_BATCH ? 1 : 0, filt_off, filt_ids, w.state, nq,
+                                              m->nentity, m->nrelation, w.bits, err_flag, s));
+  else
+    st = launch_status(launch_filter_bits(filt_off, filt_ids, w.state, nq, m->nentity, w.bits, err_flag, s));
+  if (st) return st;
+  // 3. the partial lists
+  if (tile) {
+    const bool prot = m->model == KGE_PROTATE;
+    if (prot) {
+      st = launch_status(launch_prot_phase(m->entity_embedding, m->nentity, K, a.c.kappa_p, 1, w.eph, s));
+      if (!st) st = launch_status(launch_prot_phase(w.q, nq, K, 0.f, 0, w.qph, s));
+      if (st) return st;
+    }
+    TopkTileArgs b;
+    memset(&b, 0, sizeof(b));
+    b.t.q = w.q; b.t.ent = m->entity_embedding; b.t.modulus = m->modulus;
+    b.t.nq = nq; b.t.E = m->nentity; b.t.Le = m->entity_dim; b.t.K = K;
+    b.t.c = a.c; b.t.true_id = w.state; b.t.fbits = w.bits; b.t.W = W;
+    b.t.qph = w.qph; b.t.eph = w.eph;
+    b.k = k; b.parts = parts; b.span = span; b.pscore = w.pscore; b.pid = w.pid;
+    st = launch_status(ops.topk_tile(md, b, s));
+  } else {
+    a.stage = 1;
+    st = launch_status(ops.topk(md, geo.vec, geo.ns, a, s));
+  }
+  if (st) return st;
+  // 4. the merge
+  return launch_status(launch_topk_merge(w.pscore, w.pid, w.state, nq, parts, k, ids_out, scores_out, s));
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -1744,6 +1860,22 @@ int kge_rank_filtered_both(const kge_model_desc* m, const int64_t* queries, int6
   c.ties_out = ties_out;
   c.listed_out = listed_out;
   return rank_impl(c);
+}
+
+size_t kge_topk_workspace_bytes(const kge_model_desc* m, int64_t nq, int32_t k, int32_t parts) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0 || k < 1 || k > KGE_TOPK_MAX_K || parts < 0) return 0;
+  int64_t span = 0;
+  size_t b = 0;
+  carve_topk(nullptr, m, nq, k, topk_parts(m, nq, parts, &span), &b);
+  return b;
+}
+
+int kge_topk(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq, const int64_t* filt_off,
+             const int64_t* filt_ids, int32_t k, int64_t* ids_out, float* scores_out, int32_t path, int32_t parts,
+             void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  return topk_impl(m, mode, queries, nq, filt_off, filt_ids, k, ids_out, scores_out, path, parts, workspace,
+                   workspace_bytes, err_flag, stream);
 }
 
 int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,

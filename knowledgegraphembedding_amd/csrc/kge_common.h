@@ -72,6 +72,9 @@ struct EmitArgs {
   int64_t ltag_v[3];
 };
 int launch_rank_emit(const EmitArgs& a, hipStream_t s);
+// kge_topk's reduction of every query's `parts` partial lists (kge_common.hip)
+int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
+                      int64_t* ids_out, float* scores_out, hipStream_t s);
 size_t csr_scan_temp_bytes(int64_t nb);
 int launch_csr(const CsrArgs& a, hipStream_t s);
 int launch_rel_rows(const RelArgs& a, hipStream_t s);

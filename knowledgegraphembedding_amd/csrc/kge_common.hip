@@ -232,4 +232,62 @@ int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float b
   return (int)hipGetLastError();
 }
 
+namespace {
+// kge_topk's merge: one wave per query.  Lane l walks partial list l (parts ≤
+// 64), each sorted by (score descending, id ascending); every output place
+// takes the best head of the 64 by a butterfly over that order (ids are
+// distinct across parts, so the winner is one lane's).  Unused places of a
+// list hold (−∞, TOPK_NO_ID) and lose to every candidate; they come out as the
+// padding (id −1, score −∞).  A query with an id out of range: (−1, NaN).
+__global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ pscore, const int32_t* __restrict__ pid,
+                                                    const int64_t* __restrict__ state, int64_t nq, int parts, int k,
+                                                    int64_t* __restrict__ ids_out, float* __restrict__ scores_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  if (state[q] != TOPK_VALID) {
+    for (int p = lane; p < k; p += 64) {
+      ids_out[q * k + p] = -1;
+      scores_out[q * k + p] = __builtin_nanf("");
+    }
+    return;
+  }
+  const bool has = lane < parts;
+  const int64_t base = (q * parts + (has ? lane : 0)) * k;
+  int head = 0;
+  float hs = has ? pscore[base] : -__builtin_inff();
+  int32_t hi = has ? pid[base] : TOPK_NO_ID;
+  for (int o = 0; o < k; ++o) {
+    float bs = hs;
+    int32_t bi = hi;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+      const float os = __shfl_xor(bs, d);
+      const int32_t oi = __shfl_xor(bi, d);
+      if (os > bs || (os == bs && oi < bi)) {
+        bs = os;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      ids_out[q * k + o] = (bi == TOPK_NO_ID) ? -1 : (int64_t)bi;
+      scores_out[q * k + o] = (bi == TOPK_NO_ID) ? -__builtin_inff() : bs;
+    }
+    if (has && hi == bi && bi != TOPK_NO_ID) {
+      ++head;
+      hs = (head < k) ? pscore[base + head] : -__builtin_inff();
+      hi = (head < k) ? pid[base + head] : TOPK_NO_ID;
+    }
+  }
+}
+}  // namespace
+
+int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
+                      int64_t* ids_out, float* scores_out, hipStream_t s) {
+  if (parts < 1 || parts > 64 || k < 1) return -1;
+  hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, pscore, pid, state, nq, parts, k,
+                     ids_out, scores_out);
+  return (int)hipGetLastError();
+}
+
 }  // namespace kge

@@ -294,6 +294,46 @@ struct TileArgs {
   const float* eph;        // pRotatE: [E, K, 2] (cos, sin) of the candidate phases
 };
 
+// Top-k link prediction (kge_topk).  The candidate table is cut into `parts`
+// ranges of `span` candidates (a multiple of 64); every (query, part) keeps a
+// list of its k best unexcluded candidates sorted by (score descending, id
+// ascending) and writes it to pscore / pid [nq, parts, k] (unused places:
+// score −∞, id INT32_MAX); k_topk_merge reduces a query's lists.
+// k_topk_prep / k_topk_scan (stage 0 / 1):
+struct TopkArgs {
+  const float* ent;
+  const float* rel;
+  const float* modulus;
+  const int64_t* queries;
+  int64_t nq, E, R;
+  int Le, Lr;
+  RowGeom eg;
+  Consts c;
+  float* q;               // [nq, Le]
+  int64_t* qsan;          // [nq, 3] the queries with the predicted column set to 0 (the filter table's lookup)
+  int64_t* state;         // [nq] TOPK_VALID, or TOPK_BAD for a query with an id out of range
+  const uint32_t* fbits;  // [nq, W] excluded candidates
+  int64_t W;
+  int k, parts;
+  int64_t span;
+  float* pscore;
+  int32_t* pid;
+  int32_t* err;
+  int stage;
+};
+// (both negative: the bitmap launches read state as "true id", and set no bit for it)
+constexpr int64_t TOPK_VALID = -1, TOPK_BAD = -2;
+constexpr int32_t TOPK_NO_ID = 0x7fffffff;
+
+// k_topk_tile: t.true_id = the queries' state; t.s_true, t.gt, t.win unused
+struct TopkTileArgs {
+  TileArgs t;
+  int k, parts;
+  int64_t span;
+  float* pscore;
+  int32_t* pid;
+};
+
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {
   Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
@@ -324,6 +364,8 @@ struct ModelOps {
   int (*rank)(int mode, int vec, int ns, const RankArgs&, hipStream_t);
   int (*rank_tile)(int mode, int gather, const TileArgs&, hipStream_t);
   int (*rank_ref)(int mode, RefStage, const RefArgs&, hipStream_t);
+  int (*topk)(int mode, int vec, int ns, const TopkArgs&, hipStream_t);
+  int (*topk_tile)(int mode, const TopkTileArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

@@ -13,6 +13,8 @@
 //                  fp32 passes counting the clear cases, listing near-ties)
 //   k_rank_window / k_rank_refine / k_rank_exact   the near-tie refinement in the
 //                  reference's own fp32 operation order (kge_rank_ref.h)
+//   k_topk_prep / k_topk_tile / k_topk_scan   top-k link prediction (kge_topk): the
+//                  ranking's all-entity passes with a selecting epilogue
 #include "kge_internal.h"
 #include "kge_rank_ref.h"
 #include "kge_rel.h"
@@ -1566,6 +1568,183 @@ struct TileMath {
   }
 };
 
+// k_topk_tile's copy of k_rank_tile's staging geometry and reduction loop
+// (below: TileCfg, tile_reduce).  k_rank_tile keeps its own text: calling the
+// shared function changed its register allocation and schedule, and the
+// ranking kernels are held to the instructions they were measured with.
+template <int M, bool SPLT>
+struct TileCfg {
+  static constexpr bool CPLX = Traits<M>::cplx;
+  static constexpr bool PROT = (M == PROTATE);
+  static constexpr int P = CPLX ? 2 : 1;             // float4 loads per staged slot
+  static constexpr int PS = (CPLX || PROT) ? 2 : 1;  // floats staged per element
+  static constexpr int T = TILE_RQ, BK = TILE_BK;
+  // SPL (TransE): the queries are staged pre-splatted, [k][row][q, q], so
+  // each packed operand of the inner loop is a plain register pair (no op_sel
+  // splat, which hipcc materialised with a v_mov for half the pairs).
+  // pRotatE staged the same way, [k][row][sin, sin, cos, cos],
+  // measured slower (whole evaluation 12.89-13.14 vs 12.61-12.68 ms, same box:
+  // twice the query LDS, fewer waves) and keeps the (sin, cos) pairs.
+  static constexpr bool SPL = SPLT && (M == TRANSE);
+  static constexpr int QW = SPL ? 2 : PS;  // floats per query per k-row of Qs
+  // TransE (SPL) and pRotatE: k-rows padded by 4 floats, so a 16-lane
+  // group's staging stores (4 rows × 4 k-offsets) fall on 16 different banks;
+  // unpadded, the k-offsets' rows are 128 or 64 floats apart, a multiple of
+  // the bank count (4-way conflicts).  pRotatE's tile: SQ_LDS_BANK_CONFLICT
+  // 4.0e8 → 1.4e8 cycles per wn18rr direction, evaluation 12.8-13.1 →
+  // 11.8 ms (`profiles/r06/rank/`).  RotatE measured slower padded (FB15k
+  // 24.4-24.5 → 25.9-26.5 ms) and stays unpadded, as do ComplEx and DistMult.
+  static constexpr int PAD = (SPL || PROT) ? 4 : 0;
+  static constexpr int QSTR = T * QW + PAD, ESTR = T * PS + PAD;
+};
+
+// One 64 × 64 tile's reduction, as k_rank_tile's: rows q0.. of q against rows
+// e0.. of the table (GATHER: the rows arow / brow name), every pair's sum left
+// in acc.  Ends on a barrier, so Qs / Es may be restaged at once.
+template <int M, int MODE, bool GATHER, bool SPLT>
+__device__ __forceinline__ void tile_reduce(const TileArgs& a, const Consts& c, int64_t q0, int64_t e0,
+                                            const int64_t* arow, const int64_t* brow,
+                                            float (&Qs)[TILE_BK][TileCfg<M, SPLT>::QSTR],
+                                            float (&Es)[TILE_BK][TileCfg<M, SPLT>::ESTR], tf2 (&acc)[4][2]) {
+  using C_ = TileCfg<M, SPLT>;
+  constexpr bool CPLX = C_::CPLX, PROT = C_::PROT, SPL = C_::SPL;
+  constexpr int P = C_::P, T = C_::T, BK = C_::BK;
+  const int t = threadIdx.x;
+  const int ty = t >> 4, tx = t & 15;
+  // staging role: row sr, elements sk .. sk+3 of the slab (K % 4 == 0, so a
+  // float4 is either wholly inside the row or wholly padding; padding terms
+  // are phi(0, 0) = 0 for every model)
+  const int sr = t >> 2, sk = (t & 3) * 4;
+  const int64_t qrow = GATHER ? arow[sr] : 0, erow = GATHER ? brow[sr] : 0;  // (read by the gather pass only)
+  // pRotatE reads the precomputed phase tables ([row][K][2], 2 float4 per
+  // staged slot); complex rows their re and im halves; real rows one float4
+  const float* qp = PROT ? a.qph + (qrow >= 0 ? qrow : 0) * (int64_t)(2 * a.K) + 2 * sk
+                         : a.q + (qrow >= 0 ? qrow : 0) * (int64_t)a.Le + sk;
+  const float* ep = PROT ? a.eph + (erow >= 0 ? erow : 0) * (int64_t)(2 * a.K) + 2 * sk
+                         : a.ent + (erow >= 0 ? erow : 0) * (int64_t)a.Le + sk;
+  constexpr int PF = PROT ? 2 : P;  // float4 loads per staged slot
+  float4 rq[PF], re[PF];
+  // counting pass: the block's 64 query rows and 64 candidate rows are each
+  // contiguous, so one buffer descriptor per operand covers them and a row
+  // past nq / E, or a slot past K, reads 0 from the hardware range check (its
+  // offset set to the range's end) — no zero-fill moves and no branches
+  const int64_t rlen = PROT ? 2 * (int64_t)a.K : a.Le;  // floats per staged row
+  // (built in the gather pass too, where no load goes through them)
+  const int64_t nqr = (a.nq - q0 < T) ? a.nq - q0 : T, ner = (a.E - e0 < T) ? a.E - e0 : T;
+  const uint32_t qend = (uint32_t)(nqr * rlen * 4), eend = (uint32_t)((ner > 0 ? ner : 0) * rlen * 4);
+  const auto qrs = buf_rsrc((PROT ? a.qph : a.q) + q0 * rlen, qend);
+  const auto ers = buf_rsrc((PROT ? a.eph : a.ent) + (GATHER ? 0 : e0) * rlen, eend);
+  auto fetch = [&](int k0) {
+    const bool in = (k0 + sk) < a.K;
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      const int64_t o = PROT ? (int64_t)2 * k0 + 4 * p : (int64_t)p * a.K + k0;
+      if constexpr (GATHER) {
+        rq[p] = (in && qrow >= 0) ? *reinterpret_cast<const float4*>(qp + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+        re[p] = (in && erow >= 0) ? *reinterpret_cast<const float4*>(ep + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        const uint32_t off = (uint32_t)((sr * rlen + (PROT ? 2 * sk : sk) + o) * 4);
+        float x[4], y[4];
+        buf_ld4(qrs, in ? off : qend, x);
+        buf_ld4(ers, in ? off : eend, y);
+        rq[p] = make_float4(x[0], x[1], x[2], x[3]);
+        re[p] = make_float4(y[0], y[1], y[2], y[3]);
+      }
+    }
+  };
+  fetch(0);
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = tf2{0.f, 0.f};
+
+  for (int k0 = 0; k0 < a.K; k0 += BK) {
+    if constexpr (CPLX) {
+      const float qr[4] = {rq[0].x, rq[0].y, rq[0].z, rq[0].w}, qi[4] = {rq[1].x, rq[1].y, rq[1].z, rq[1].w};
+      const float er[4] = {re[0].x, re[0].y, re[0].z, re[0].w}, ei[4] = {re[1].x, re[1].y, re[1].z, re[1].w};
+      // (RotatE: candidate sr's re at Es column sr, its im at T + sr;
+      // ComplEx: its (re, im) pair in half (sr / 2) % 2 at (sr / 4)·4 + 2·(sr % 2))
+      const int ec = ((sr & 2) ? T : 0) + (sr >> 2) * 4 + 2 * (sr & 1);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qr[u], qi[u]};
+        if constexpr (M == ROTATE) {
+          Es[sk + u][sr] = er[u];
+          Es[sk + u][T + sr] = ei[u];
+        } else {
+          *reinterpret_cast<tf2*>(&Es[sk + u][ec]) = tf2{er[u], ei[u]};
+        }
+      }
+    } else if constexpr (PROT) {
+      // (sin q, cos q) and (cos e, sin e) of the candidate phase e / (range / π)
+      // (model.py:245-246), evaluated once per element by launch_prot_phase
+      // (Qs: query sr's (sin, cos) at 2·sr; Es: candidate sr's cos at
+      // column sr, its sin at T + sr)
+#pragma unroll
+      for (int u = 0; u < 4; u += 2) {
+        const float4 qv = rq[u >> 1], ev = re[u >> 1];
+        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qv.x, qv.y};
+        *reinterpret_cast<tf2*>(&Qs[sk + u + 1][2 * sr]) = tf2{qv.z, qv.w};
+        Es[sk + u][sr] = ev.x;
+        Es[sk + u][T + sr] = ev.y;
+        Es[sk + u + 1][sr] = ev.z;
+        Es[sk + u + 1][T + sr] = ev.w;
+      }
+    } else if constexpr (SPL) {
+      // TransE: query sr's element as the pair (q, q) at 2·sr
+      const float4 e4 = re[0];
+      *reinterpret_cast<tf2*>(&Qs[sk + 0][2 * sr]) = tf2{rq[0].x, rq[0].x};
+      *reinterpret_cast<tf2*>(&Qs[sk + 1][2 * sr]) = tf2{rq[0].y, rq[0].y};
+      *reinterpret_cast<tf2*>(&Qs[sk + 2][2 * sr]) = tf2{rq[0].z, rq[0].z};
+      *reinterpret_cast<tf2*>(&Qs[sk + 3][2 * sr]) = tf2{rq[0].w, rq[0].w};
+      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
+      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
+    } else {
+      const float4 e4 = re[0];
+      Qs[sk + 0][sr] = rq[0].x; Qs[sk + 1][sr] = rq[0].y;
+      Qs[sk + 2][sr] = rq[0].z; Qs[sk + 3][sr] = rq[0].w;
+      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
+      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
+    }
+    __syncthreads();
+    if (k0 + BK < a.K) fetch(k0 + BK);
+    if constexpr (SPL) {
+      // the next k's LDS operands are read before this k's arithmetic (the
+      // unroll-4 loop waited on every k's reads: lgkmcnt(0) in front of its math)
+      float4 ql[2][2], el[2];
+      auto lds_ld = [&](int k, float4 (&qv)[2], float4& ev) {
+        qv[0] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
+        qv[1] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
+        ev = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
+      };
+      lds_ld(0, ql[0], el[0]);
+#pragma unroll
+      for (int k = 0; k < BK; ++k) {
+        if (k + 1 < BK) lds_ld(k + 1, ql[(k + 1) & 1], el[(k + 1) & 1]);
+        TileMath<M, MODE>::transe_spl(ql[k & 1], el[k & 1], acc);
+      }
+    } else
+#pragma unroll 4
+    for (int k = 0; k < BK; ++k) {
+      if constexpr (CPLX || PROT) {
+        const float4 qa = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
+        const float4 qb = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
+        const float4 ea = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
+        const float4 eb = *reinterpret_cast<const float4*>(&Es[k][T + tx * 4]);
+        const tf2 q2[4] = {tf2{qa.x, qa.y}, tf2{qa.z, qa.w}, tf2{qb.x, qb.y}, tf2{qb.z, qb.w}};
+        const tf2 e2[4] = {tf2{ea.x, ea.y}, tf2{ea.z, ea.w}, tf2{eb.x, eb.y}, tf2{eb.z, eb.w}};
+        if constexpr (PROT) TileMath<M, MODE>::prot(q2, ea, eb, acc);
+        else if constexpr (M == ROTATE) TileMath<M, MODE>::rot(q2, ea, eb, acc);
+        else TileMath<M, MODE>::cplx(q2, e2, acc);
+      } else {
+        const float4 q4 = *reinterpret_cast<const float4*>(&Qs[k][ty * 4]);
+        const float4 e4 = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
+        TileMath<M, MODE>::real(q4, e4, acc, c);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 template <int M, int MODE, bool GATHER, bool SPLT = true>
 __global__ __launch_bounds__(256) void k_rank_tile(TileArgs a) {
   constexpr bool CPLX = Traits<M>::cplx;
@@ -1815,6 +1994,238 @@ int launch_rank_tile(int mode, int gather, const TileArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((k_rank_tile<M, TAIL_BATCH, false>), dim3(gx, gy), dim3(256), 0, s, a);
   }
   return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------- top-k prediction
+// kge_topk: each (query, candidate part) keeps the k best unexcluded
+// candidates of its part as a list sorted by (score descending, id ascending)
+// in LDS, owned by one wave; k_topk_merge (kge_common.hip) reduces a query's
+// parts.  Unused places hold (−∞, TOPK_NO_ID), so a list is always "full" and
+// its last place is the threshold a new candidate has to beat.
+
+// One wave inserts (s, e) into its sorted k-list (k ≤ 128: places lane and
+// lane + 64) and returns the new threshold.  Wave-uniform arguments; LDS
+// operations of one wave execute in order, so the moved entries are read
+// before any place is overwritten.
+__device__ __forceinline__ float topk_insert(volatile float* ls, volatile int32_t* li, int k, float s, int32_t e,
+                                             int lane) {
+  const int p0 = lane, p1 = lane + 64;
+  const bool in0 = p0 < k, in1 = p1 < k;
+  const float s0 = in0 ? ls[p0] : 0.f, s1 = in1 ? ls[p1] : 0.f;
+  const int32_t i0 = in0 ? li[p0] : 0, i1 = in1 ? li[p1] : 0;
+  // the places that stay ahead of the new entry (a prefix: the list is sorted)
+  const bool a0 = in0 && (s0 > s || (s0 == s && i0 < e));
+  const bool a1 = in1 && (s1 > s || (s1 == s && i1 < e));
+  const int pos = __popcll(__ballot(a0)) + __popcll(__ballot(a1));
+  if (pos < k) {
+    const bool w0 = in0 && p0 > pos, w1 = in1 && p1 > pos;
+    const float m0 = w0 ? ls[p0 - 1] : 0.f, m1 = w1 ? ls[p1 - 1] : 0.f;
+    const int32_t j0 = w0 ? li[p0 - 1] : 0, j1 = w1 ? li[p1 - 1] : 0;
+    __builtin_amdgcn_wave_barrier();
+    if (w0) { ls[p0] = m0; li[p0] = j0; }
+    if (w1) { ls[p1] = m1; li[p1] = j1; }
+    if (p0 == pos) { ls[p0] = s; li[p0] = e; }
+    if (p1 == pos) { ls[p1] = s; li[p1] = e; }
+    __builtin_amdgcn_wave_barrier();
+  }
+  return ls[k - 1];
+}
+
+// a wave writes one list to its place of the partial lists
+__device__ __forceinline__ void topk_store(const TopkArgs& a, int64_t q, int part, const volatile float* ls,
+                                           const volatile int32_t* li, int lane) {
+  const int64_t dst = (q * a.parts + part) * a.k;
+  for (int p = lane; p < a.k; p += 64) {
+    a.pscore[dst + p] = ls[p];
+    a.pid[dst + p] = li[p];
+  }
+}
+
+// q of every query (one wave each), as k_rank_prep builds it with device
+// cos / sin, without the true entity: the predicted column is neither read for
+// a row nor range-checked.  A query whose other two ids are out of range sets
+// KGE_DEVERR_INDEX and is marked TOPK_BAD.
+template <int M, int MODE, int VEC, int NS>
+__global__ __launch_bounds__(256) void k_topk_prep(TopkArgs a) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  using R_ = Row<NS, VEC, CPLX>;
+  const int lane = threadIdx.x & 63;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + wave_id();
+  if (qi >= a.nq) return;
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  const int64_t x = (MODE == HEAD_BATCH) ? t : h;
+  const bool bad = x < 0 || x >= a.E || r < 0 || r >= a.R;
+  if (lane == 0) {
+    a.qsan[qi * 3] = (MODE == HEAD_BATCH) ? 0 : h;
+    a.qsan[qi * 3 + 1] = r;
+    a.qsan[qi * 3 + 2] = (MODE == HEAD_BATCH) ? t : 0;
+    a.state[qi] = bad ? TOPK_BAD : TOPK_VALID;
+    if (bad) atomicOr(a.err, KGE_DEVERR_INDEX);
+  }
+  if (bad) return;
+  R_ q, xr, rr;
+  load_row<NS, VEC, CPLX>(a.ent + x * a.Le, a.eg, lane, xr);
+  load_rel<M, NS, VEC, CPLX>(a.rel + r * a.Lr, a.eg, lane, rr);
+  build_q<M, MODE, NS, VEC, CPLX>(xr, rr, c, q);
+  store_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
+}
+
+// Wave-scan top-k (any row the register kernels hold): one wave per (query,
+// part) scores its candidates in ascending id as k_rank_scan does and offers
+// those that beat the list's threshold.
+template <int M, int MODE, int VEC, int NS>
+__global__ __launch_bounds__(256) void k_topk_scan(TopkArgs a) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  using R_ = Row<NS, VEC, CPLX>;
+  __shared__ float lss[4][KGE_TOPK_MAX_K];
+  __shared__ int32_t lis[4][KGE_TOPK_MAX_K];
+  const int lane = threadIdx.x & 63, w = wave_id();
+  const int64_t unit = (int64_t)blockIdx.x * 4 + w;
+  if (unit >= a.nq * a.parts) return;
+  const int64_t qi = unit / a.parts;
+  const int part = (int)(unit - qi * a.parts);
+  const int64_t c0 = part * a.span;
+  const int64_t c1 = (c0 + a.span < a.E) ? (c0 + a.span) : a.E;
+  volatile float* ls = lss[w];
+  volatile int32_t* li = lis[w];
+  for (int p = lane; p < a.k; p += 64) {
+    ls[p] = -__builtin_inff();
+    li[p] = TOPK_NO_ID;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (a.state[qi] == TOPK_VALID) {
+    Consts c = a.c;
+    if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+    const uint32_t* bits = a.fbits + qi * a.W;
+    R_ q;
+    load_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
+    float thr = -__builtin_inff();
+    for (int64_t e = c0; e < c1; ++e) {
+      if ((bits[e >> 5] >> (e & 31)) & 1u) continue;  // wave-uniform
+      R_ r0;
+      load_row<NS, VEC, CPLX>(a.ent + e * a.Le, a.eg, lane, r0);
+      const float s0 = Elem<M, MODE>::finish(wave_sum(lane_total<M, MODE, NS, VEC, CPLX>(q, r0, c)), c);
+      if (s0 > thr) thr = topk_insert(ls, li, a.k, s0, (int32_t)e, lane);  // (false for NaN)
+    }
+  }
+  topk_store(a, qi, part, ls, li, lane);
+}
+
+// Register-tile top-k: a workgroup takes 64 queries and one candidate part and
+// walks the part's 64-candidate tiles in ascending id with k_rank_tile's
+// reduction (tile_reduce).  A query's 64 scores of a tile sit in the 16 lanes
+// of one wave (its row of the 4 × 4 thread blocks), so its list is that wave's
+// alone: no block-wide step in the epilogue.  Each lane keeps its four
+// queries' thresholds in registers; a pair costs the filter bit and one
+// compare, and only pairs that beat the threshold are offered — one at a time
+// per wave, lowest lane and candidate first, which is ascending id within a
+// query.  After an offer the row's threshold moves and its waiting pairs are
+// re-screened.  A score equal to the threshold comes from a higher id than
+// every listed one (ids ascend within the part), so it loses: the tie rule.
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_topk_tile(TopkTileArgs b) {
+  const TileArgs& a = b.t;
+  using C_ = TileCfg<M, true>;
+  constexpr int T = C_::T, BK = C_::BK;
+  __shared__ __attribute__((aligned(16))) float Qs[BK][C_::QSTR];
+  __shared__ __attribute__((aligned(16))) float Es[BK][C_::ESTR];
+  extern __shared__ __attribute__((aligned(16))) float tk_lists[];  // [T][k] scores, then [T][k] ids
+  const int k = b.k;
+  volatile float* lsb = tk_lists;
+  volatile int32_t* lib = reinterpret_cast<int32_t*>(tk_lists + T * k);
+  const int t = threadIdx.x, lane = t & 63, w = wave_id();
+  const int ty = t >> 4, tx = t & 15;
+  const int64_t q0 = (int64_t)blockIdx.y * T;
+  const int part = blockIdx.x;
+  const int64_t c0 = part * b.span;
+  const int64_t c1 = (c0 + b.span < a.E) ? (c0 + b.span) : a.E;
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  for (int i = t; i < T * k; i += 256) {
+    lsb[i] = -__builtin_inff();
+    lib[i] = TOPK_NO_ID;
+  }
+  bool rowok[4];
+  float thr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t q = q0 + ty * 4 + i;
+    rowok[i] = q < a.nq && a.true_id[q] == TOPK_VALID;
+    thr[i] = -__builtin_inff();
+  }
+  __syncthreads();
+
+  for (int64_t e0 = c0; e0 < c1; e0 += T) {
+    tf2 acc[4][2];
+    tile_reduce<M, MODE, false, true>(a, c, q0, e0, nullptr, nullptr, Qs, Es, acc);
+    auto pair_total = [&](int i, int j) -> float { return (j & 1) ? acc[i][j >> 1].y : acc[i][j >> 1].x; };
+    const int64_t eb0 = e0 + tx * 4;  // four candidates in one bitmap word
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float s[4];
+      uint32_t pm = 0u;  // this lane's pairs of row i that wait to be offered
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = Elem<M, MODE>::finish(pair_total(i, j), c);
+      if (rowok[i] && eb0 < a.E) {
+        const uint32_t word = a.fbits[(q0 + ty * 4 + i) * a.W + (eb0 >> 5)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int64_t e = eb0 + j;
+          const bool ok = (e < a.E) && (((word >> (e & 31)) & 1u) == 0u);
+          if (ok && s[j] > thr[i]) pm |= 1u << j;  // (false for NaN)
+        }
+      }
+      uint64_t waiting = __ballot(pm != 0u);
+      while (waiting) {  // the rare path
+        const int L = __builtin_ctzll(waiting);
+        const int jn = pm ? __builtin_ctz(pm) : 0;
+        const float sn = (jn == 0) ? s[0] : (jn == 1) ? s[1] : (jn == 2) ? s[2] : s[3];
+        const int jL = __builtin_amdgcn_readlane(jn, L);
+        const float sL = readlanef(sn, L);
+        const int row = (w * 4 + (L >> 4)) * 4 + i;
+        const int32_t eL = (int32_t)(e0 + (L & 15) * 4 + jL);
+        const float nt = topk_insert(lsb + row * k, lib + row * k, k, sL, eL, lane);
+        if (lane == L) pm &= pm - 1u;
+        if ((lane >> 4) == (L >> 4)) {
+          thr[i] = nt;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (!(s[j] > nt)) pm &= ~(1u << j);
+        }
+        waiting = __ballot(pm != 0u);
+      }
+    }
+  }
+  // each wave writes its 16 rows' lists
+  for (int r = 0; r < 16; ++r) {
+    const int row = w * 16 + r;
+    const int64_t q = q0 + row;
+    if (q >= a.nq) break;
+    const int64_t dst = (q * b.parts + part) * k;
+    for (int p = lane; p < k; p += 64) {
+      b.pscore[dst + p] = lsb[row * k + p];
+      b.pid[dst + p] = lib[row * k + p];
+    }
+  }
+}
+
+template <int M>
+int launch_topk_tile(int mode, const TopkTileArgs& b, hipStream_t s) {
+  const dim3 grid((unsigned)b.parts, (unsigned)((b.t.nq + TILE_RQ - 1) / TILE_RQ));
+  const size_t lds = (size_t)TILE_RQ * b.k * (sizeof(float) + sizeof(int32_t));
+  auto go = [&](auto kern) {
+    // the lists of k > 64 pass the 64 KB a launch may use without asking
+    if (lds > 32768) {
+      const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (he != hipSuccess) return (int)he;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, b);
+    return (int)hipGetLastError();
+  };
+  return (mode == HEAD_BATCH) ? go(k_topk_tile<M, HEAD_BATCH>) : go(k_topk_tile<M, TAIL_BATCH>);
 }
 
 // ---------------------------------------------- near-tie refinement
@@ -2636,6 +3047,23 @@ struct RunEntity { static int run(const EntArgs& a, hipStream_t s) { return Laun
 template <int M, int MODE, int VEC, int NS>
 struct RunRank { static int run(const RankArgs& a, hipStream_t s) { return Launch<M, MODE, VEC, NS>::rank(a, s); } };
 
+template <int M, int MODE, int VEC, int NS>
+struct RunTopk {
+  static int run(const TopkArgs& a, hipStream_t s) {
+    if constexpr (NS == 0) {
+      return -1;  // rows wider than the register kernels hold: not served (KGE_ERR_DIM)
+    } else {
+      if (a.stage == 0) {
+        hipLaunchKernelGGL((k_topk_prep<M, MODE, VEC, NS>), dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, s, a);
+      } else {
+        const int64_t units = a.nq * a.parts;
+        hipLaunchKernelGGL((k_topk_scan<M, MODE, VEC, NS>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);
+      }
+      return (int)hipGetLastError();
+    }
+  }
+};
+
 template <int M>
 struct ModelTable {
   static int score(int mode, int vec, int ns, const ScoreArgs& a, int64_t u, hipStream_t s) {
@@ -2649,6 +3077,9 @@ struct ModelTable {
   }
   static int rank(int mode, int vec, int ns, const RankArgs& a, hipStream_t s) {
     return dispatch<M, RunRank>(mode, vec, ns, a, s);
+  }
+  static int topk(int mode, int vec, int ns, const TopkArgs& a, hipStream_t s) {
+    return dispatch<M, RunTopk>(mode, vec, ns, a, s);
   }
 };
 
@@ -2664,6 +3095,8 @@ struct ModelTable {
     o.rank = &ModelTable<M>::rank;                                                                 \
     o.rank_tile = &launch_rank_tile<M>;                                                            \
     o.rank_ref = &launch_rank_ref<M>;                                                              \
+    o.topk = &ModelTable<M>::topk;                                                                 \
+    o.topk_tile = &launch_topk_tile<M>;                                                            \
     return o;                                                                                      \
   }                                                                                                \
   }

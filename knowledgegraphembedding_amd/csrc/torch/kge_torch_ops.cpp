@@ -7,6 +7,7 @@
 //   kge::score_backward    its autograd (dense IndexSelectBackward + index_add_)
 //   kge::train_step_grads  train_step up to loss.backward()       model.py:252-301
 //   kge::rank_filtered     test_step's filtered ranking           model.py:383-418
+//   kge::topk              top-k link prediction (no reference counterpart: forward + torch.topk)
 //   kge::sample_negatives  TrainDataset.__getitem__ + collate_fn  dataloader.py:34-66
 //   kge::error_flag        the device error flag the kernels OR into (IndexError on read)
 //
@@ -387,6 +388,61 @@ std::tuple<Tensor, Tensor> rank_filtered_meta(const Tensor& entity, const Tensor
           at::empty_symint({queries.sym_size(0)}, o.dtype(at::kInt))};
 }
 
+// -------------------------------------------------------------------- top-k
+// kge_topk with per-query filter lists (filt_off [nq + 1], filt_ids) or none;
+// more than 65535 queries go in several calls
+std::tuple<Tensor, Tensor> topk_cuda(const Tensor& entity, const Tensor& relation, const optional<Tensor>& modulus,
+                                     const Tensor& queries, const optional<Tensor>& filt_off,
+                                     const optional<Tensor>& filt_ids, int64_t mode, int64_t model, double gamma,
+                                     double erange, int64_t k, int64_t path) {
+  check_model_mode(model, mode, true);
+  TORCH_CHECK_VALUE(path == 0 || path == 2 || path == 3, "top-k path ", path,
+                    " not supported (0 auto, 2 tile, 3 scan)");
+  TORCH_CHECK_VALUE(k >= 1 && k <= KGE_TOPK_MAX_K, "k = ", k, ": expected 1 .. ", KGE_TOPK_MAX_K);
+  const c10::Device dev = require_device({&entity, &relation, modulus ? &*modulus : nullptr, &queries});
+  c10::DeviceGuard guard(dev);
+  kge_model_desc d = make_desc(model, entity, relation, gamma, erange, modulus);
+  const Tensor q = as_index(queries, dev);
+  TORCH_CHECK(q.dim() == 2 && q.size(1) == 3, "queries must be [nq, 3], got ", q.sizes());
+  const int64_t nq = q.size(0);
+  const bool filtered = filt_off.has_value() && filt_off->defined();
+  Tensor off, ids;
+  if (filtered) {
+    TORCH_CHECK(filt_ids.has_value() && filt_ids->defined(), "filt_off without filt_ids");
+    off = as_index(*filt_off, dev);
+    TORCH_CHECK(off.numel() == nq + 1, "filt_off must hold nq + 1 = ", nq + 1, " offsets, got ", off.numel());
+    ids = filt_ids->numel() ? as_index(*filt_ids, dev)
+                            : at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(dev));
+  }
+  Tensor out_ids = at::empty({nq, k}, at::TensorOptions().dtype(at::kLong).device(dev));
+  Tensor out_s = at::empty({nq, k}, at::TensorOptions().dtype(at::kFloat).device(dev));
+  int32_t* err = error_flag_for(dev).data_ptr<int32_t>();
+  void* st = current_stream(dev);
+  for (int64_t c0 = 0; c0 < nq; c0 += 65535) {
+    const int64_t n = std::min<int64_t>(65535, nq - c0);
+    Tensor ws = workspace(kge_topk_workspace_bytes(&d, n, (int32_t)k, 0), dev);
+    // (a chunk's offsets still index the whole filt_ids)
+    check_status(kge_topk(&d, (int32_t)mode, q.data_ptr<int64_t>() + 3 * c0, n,
+                          filtered ? off.data_ptr<int64_t>() + c0 : nullptr,
+                          filtered ? ids.data_ptr<int64_t>() : nullptr, (int32_t)k,
+                          out_ids.data_ptr<int64_t>() + c0 * k, out_s.data_ptr<float>() + c0 * k, (int32_t)path, 0,
+                          ws.data_ptr(), (size_t)ws.numel(), err, st),
+                 "kge_topk");
+  }
+  return {out_ids, out_s};
+}
+
+std::tuple<Tensor, Tensor> topk_meta(const Tensor& entity, const Tensor& relation, const optional<Tensor>& modulus,
+                                     const Tensor& queries, const optional<Tensor>& filt_off,
+                                     const optional<Tensor>& filt_ids, int64_t mode, int64_t model, double gamma,
+                                     double erange, int64_t k, int64_t path) {
+  check_model_mode(model, mode, true);
+  TORCH_CHECK_VALUE(k >= 1 && k <= KGE_TOPK_MAX_K, "k = ", k, ": expected 1 .. ", KGE_TOPK_MAX_K);
+  auto o = queries.options();
+  return {at::empty_symint({queries.sym_size(0), c10::SymInt(k)}, o.dtype(at::kLong)),
+          at::empty_symint({queries.sym_size(0), c10::SymInt(k)}, o.dtype(at::kFloat))};
+}
+
 // ------------------------------------------------------------------ sampler
 void sample_negatives_cuda(const Tensor& triples, const Tensor& batch, int64_t nentity, int64_t negative_sample_size,
                            const Tensor& true_off, const Tensor& true_len, const Tensor& true_ids,
@@ -455,6 +511,12 @@ std::tuple<Tensor, Tensor> rank_filtered_cpu(const Tensor&, const Tensor&, const
   check_model_mode(model, mode, true);
   return refuse_cpu<std::tuple<Tensor, Tensor>>();
 }
+std::tuple<Tensor, Tensor> topk_cpu(const Tensor&, const Tensor&, const optional<Tensor>&, const Tensor&,
+                                    const optional<Tensor>&, const optional<Tensor>&, int64_t mode, int64_t model,
+                                    double, double, int64_t, int64_t) {
+  check_model_mode(model, mode, true);
+  return refuse_cpu<std::tuple<Tensor, Tensor>>();
+}
 void sample_negatives_cpu(const Tensor&, const Tensor&, int64_t, int64_t, const Tensor&, const Tensor&,
                           const Tensor&, const Tensor&, int64_t, int64_t, const Tensor&, const Tensor&,
                           const Tensor&) {
@@ -474,6 +536,8 @@ TORCH_LIBRARY(kge, m) {
   m.def("rank_filtered(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor filt_off, "
         "Tensor filt_ids, int mode, int model, float gamma, float embedding_range, int path=0, "
         "Tensor? relation_trig=None) -> (Tensor, Tensor)");
+  m.def("topk(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor? filt_off, Tensor? filt_ids, "
+        "int mode, int model, float gamma, float embedding_range, int k, int path=0) -> (Tensor, Tensor)");
   m.def("sample_negatives(Tensor triples, Tensor batch, int nentity, int negative_sample_size, Tensor true_off, "
         "Tensor true_len, Tensor true_ids, Tensor weights, int key, int max_draws, Tensor(a!) pos_out, "
         "Tensor(b!) neg_out, Tensor(c!) w_out) -> ()");
@@ -486,6 +550,7 @@ TORCH_LIBRARY_IMPL(kge, CUDA, m) {
   m.impl("score_backward", &score_backward_cuda);
   m.impl("train_step_grads", &train_step_grads_cuda);
   m.impl("rank_filtered", &rank_filtered_cuda);
+  m.impl("topk", &topk_cuda);
   m.impl("sample_negatives", &sample_negatives_cuda);
 }
 
@@ -494,6 +559,7 @@ TORCH_LIBRARY_IMPL(kge, Meta, m) {
   m.impl("score_backward", &score_backward_meta);
   m.impl("train_step_grads", &train_step_grads_meta);
   m.impl("rank_filtered", &rank_filtered_meta);
+  m.impl("topk", &topk_meta);
   m.impl("sample_negatives", &sample_negatives_meta);
 }
 
@@ -502,6 +568,7 @@ TORCH_LIBRARY_IMPL(kge, CPU, m) {
   m.impl("score_backward", &score_backward_cpu);
   m.impl("train_step_grads", &train_step_grads_cpu);
   m.impl("rank_filtered", &rank_filtered_cpu);
+  m.impl("topk", &topk_cpu);
   m.impl("sample_negatives", &sample_negatives_cpu);
 }
 

@@ -690,3 +690,37 @@ class KGEModel(nn.Module):
         res = tuple(t.cpu().numpy() for t in out)
         ops.raise_on_device_error(dev)
         return res
+
+    def predict(self, queries, mode, k=10, all_true_triples=None, path="auto"):
+        """Top-k link prediction: for every (h, r, t) row of `queries` the k
+        best tails of (h, r) (mode 'tail-batch') or heads of (r, t)
+        ('head-batch') as numpy (ids [nq, k] int64, scores [nq, k] float32),
+        best first — equal scores in ascending id — padded with (-1, -inf)
+        when fewer than k candidates remain.  The predicted column is not read
+        (pass -1).  `all_true_triples` (a triple list or a FilterIndex):
+        every known true answer of the query's (h, r) / (r, t) is excluded.
+        Scores are the fast pass's fp32 scores (ops.topk); nothing of size
+        [nq, nentity] is materialised."""
+        if mode not in ('head-batch', 'tail-batch'):
+            raise ValueError('mode %s not supported' % mode)
+        if not 1 <= int(k) <= ops.TOPK_MAX_K:
+            raise ValueError('k = %s: expected 1 .. %d' % (k, ops.TOPK_MAX_K))
+        dev = ops._require_device(self.entity_embedding)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int64).reshape(-1, 3)).copy()
+        q[:, 0 if mode == 'head-batch' else 2] = -1  # no "true" answer: only the known ones are excluded
+        filt, table = None, False
+        if all_true_triples is not None:
+            index = all_true_triples if isinstance(all_true_triples, FilterIndex) else \
+                FilterIndex(all_true_triples, self.nentity, self.nrelation, device=dev)
+            use_table = os.environ.get("KGE_RANK_FILTER_TABLE", "1") != "0"
+            filt = index.device_table(mode, dev) if use_table else None
+            table = filt is not None
+            if not table:
+                off, ids = index.filter_csr(q, mode)
+                filt = (torch.from_numpy(off), torch.from_numpy(ids))
+        with torch.no_grad():
+            ids, scores = ops.topk(self.desc(), mode, torch.from_numpy(q), int(k), dev, filt=filt, filter_table=table,
+                                   path=path)
+        res = ids.cpu().numpy(), scores.cpu().numpy()
+        ops.raise_on_device_error(dev)
+        return res

@@ -543,6 +543,55 @@ def rank_filtered_both(desc: _lib.ModelDesc, queries: torch.Tensor, filt_head, f
     return (ranks, ties, lst) if listed else (ranks, ties)
 
 
+TOPK_MAX_K = 128  # kge_hip.h KGE_TOPK_MAX_K
+TOPK_PATHS = {"auto": 0, "tile": 2, "scan": 3}
+
+
+def topk(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, k: int, dev, filt=None,
+         filter_table: bool = False, path: str = "auto", parts: int = 0):
+    """The k best candidates of every query (kge_topk): device tensors
+    (ids [nq, k] int64, scores [nq, k] float32), ordered by (score descending,
+    id ascending), padded with (-1, -inf).  mode "tail-batch" predicts tails
+    from (h, r), "head-batch" heads from (r, t); the predicted column of
+    `queries` is not read.  `filt` = (filt_off, filt_ids): the candidates to
+    exclude, per-query lists or (`filter_table`) the whole filter index, as
+    rank_filtered takes them; None: no filter.  `parts`: candidate ranges the
+    table is cut into (0: chosen by the library).  The device error flag is
+    left for the caller's next read (raise_on_device_error)."""
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("mode %s not supported" % mode)
+    if path not in TOPK_PATHS:
+        raise ValueError("top-k path %s not supported" % path)
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k = {k}: expected 1 .. {TOPK_MAX_K}")
+    k = int(k)
+    q = _idx(queries, dev)
+    nq = q.shape[0]
+    off = ids = None
+    if filt is not None:
+        _check_filter_shape(desc, nq, filt[0], filter_table)
+        off = _idx(filt[0], dev)
+        ids = _idx(filt[1], dev) if filt[1].numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+    out_ids = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    st = state(dev)
+    flags = TOPK_PATHS[path] | (_lib.RANK_FILTER_TABLE if filter_table else 0)
+    mode_id = _lib.MODE_IDS[mode]
+    for c0 in range(0, nq, 65535):  # (kge_topk: at most 65535 queries per call)
+        n = min(65535, nq - c0)
+        # per-query lists: the chunk's offsets still index the whole filt_ids
+        coff = off if (off is None or filter_table) else off[c0:c0 + n + 1]
+        ws = st.workspace(lib.kge_topk_workspace_bytes(desc, n, k, parts))
+        _lib.check(
+            lib.kge_topk(desc, mode_id, q[c0:c0 + n].data_ptr(), n, _ptr(coff), _ptr(ids), k,
+                         out_ids[c0:c0 + n].data_ptr(), out_s[c0:c0 + n].data_ptr(), flags, parts, ws.data_ptr(),
+                         ws.numel(), st.err.data_ptr(), _stream(dev)),
+            "kge_topk",
+        )
+    return out_ids, out_s
+
+
 def reference_sin(args: torch.Tensor) -> torch.Tensor:
     """sin of pRotatE phase sums as the reference evaluates them: its own
     `torch.sin` on the CPU (model.py:245; ATen's vectorized CPU kernel — MKL
