@@ -48,6 +48,8 @@ struct Consts {
   float kappa_p;  // embedding_range / pi'    (model.py:236-238, pi typo)
   float modulus;  // pRotatE modulus value, read from the device parameter
 };
+// bit e of a query's filter bitmap (1: excluded)
+__device__ __forceinline__ bool filter_bit(const uint32_t* bits, int64_t e) { return (bits[e >> 5] >> (e & 31)) & 1u; }
 
 // ---------------------------------------------------------------- loads
 typedef float tf2 __attribute__((ext_vector_type(2)));  // a register pair (v_pk_*_f32 operand)

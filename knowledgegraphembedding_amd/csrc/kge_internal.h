@@ -171,6 +171,11 @@ inline bool env_flag_off(const char* name) {
   const char* e = getenv(name);
   return e && e[0] == '0' && e[1] == 0;
 }
+// a launch's kernel by its direction: head-batch's instantiation or tail-batch's
+template <typename K>
+inline K pick_dir(int mode, K head, K tail) {
+  return mode == HEAD_BATCH ? head : tail;
+}
 
 struct RankWin {
   const float* delta;  // [nq]

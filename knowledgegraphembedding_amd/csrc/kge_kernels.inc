@@ -1396,7 +1396,7 @@ __global__ __launch_bounds__(256) void k_rank_scan(RankArgs a) {
   load_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
   int gt = 0;
   for (int64_t e = c0; e < c1; ++e) {
-    if ((bits[e >> 5] >> (e & 31)) & 1u) continue;  // wave-uniform
+    if (filter_bit(bits, e)) continue;  // wave-uniform
     R_ r0;
     load_row<NS, VEC, CPLX>(a.ent + e * a.Le, a.eg, lane, r0);
     const float s0 = Elem<M, MODE>::finish(wave_sum(lane_total<M, MODE, NS, VEC, CPLX>(q, r0, c)), c);
@@ -1568,10 +1568,16 @@ struct TileMath {
   }
 };
 
-// k_topk_tile's copy of k_rank_tile's staging geometry and reduction loop
-// (below: TileCfg, tile_reduce).  k_rank_tile keeps its own text: calling the
-// shared function changed its register allocation and schedule, and the
-// ranking kernels are held to the instructions they were measured with.
+// The staging geometry of one 64 × 64 tile (k_rank_tile, k_topk_tile).  The
+// reduction loop itself is one text, kge_tile_reduce.inc, included in
+// k_rank_tile's body and in tile_reduce, which k_topk_tile calls: a textual
+// fragment, so both kernels keep the instructions they were measured with.
+// k_rank_tile calling tile_reduce instead costs VGPRs (as it stands RotatE
+// 70 → 74, one wave per SIMD less); with the arguments by value and the staging
+// buffers the function's own it stayed within the allocation step (72 / 72 /
+// 78 / 50 / 72 VGPRs for 70 / 70 / 76 / 49 / 72) and ranked as fast, but that
+// form changed k_topk_tile, which then measured slower at k = 10 (DESIGN.md
+// §5b).
 template <int M, bool SPLT>
 struct TileCfg {
   static constexpr bool CPLX = Traits<M>::cplx;
@@ -1598,185 +1604,31 @@ struct TileCfg {
   static constexpr int QSTR = T * QW + PAD, ESTR = T * PS + PAD;
 };
 
-// One 64 × 64 tile's reduction, as k_rank_tile's: rows q0.. of q against rows
-// e0.. of the table (GATHER: the rows arow / brow name), every pair's sum left
-// in acc.  Ends on a barrier, so Qs / Es may be restaged at once.
+// One 64 × 64 tile's reduction as a function (k_topk_tile): kge_tile_reduce.inc.
 template <int M, int MODE, bool GATHER, bool SPLT>
 __device__ __forceinline__ void tile_reduce(const TileArgs& a, const Consts& c, int64_t q0, int64_t e0,
                                             const int64_t* arow, const int64_t* brow,
                                             float (&Qs)[TILE_BK][TileCfg<M, SPLT>::QSTR],
                                             float (&Es)[TILE_BK][TileCfg<M, SPLT>::ESTR], tf2 (&acc)[4][2]) {
   using C_ = TileCfg<M, SPLT>;
-  constexpr bool CPLX = C_::CPLX, PROT = C_::PROT, SPL = C_::SPL;
-  constexpr int P = C_::P, T = C_::T, BK = C_::BK;
+  constexpr int T = C_::T, BK = C_::BK;
   const int t = threadIdx.x;
   const int ty = t >> 4, tx = t & 15;
-  // staging role: row sr, elements sk .. sk+3 of the slab (K % 4 == 0, so a
-  // float4 is either wholly inside the row or wholly padding; padding terms
-  // are phi(0, 0) = 0 for every model)
-  const int sr = t >> 2, sk = (t & 3) * 4;
-  const int64_t qrow = GATHER ? arow[sr] : 0, erow = GATHER ? brow[sr] : 0;  // (read by the gather pass only)
-  // pRotatE reads the precomputed phase tables ([row][K][2], 2 float4 per
-  // staged slot); complex rows their re and im halves; real rows one float4
-  const float* qp = PROT ? a.qph + (qrow >= 0 ? qrow : 0) * (int64_t)(2 * a.K) + 2 * sk
-                         : a.q + (qrow >= 0 ? qrow : 0) * (int64_t)a.Le + sk;
-  const float* ep = PROT ? a.eph + (erow >= 0 ? erow : 0) * (int64_t)(2 * a.K) + 2 * sk
-                         : a.ent + (erow >= 0 ? erow : 0) * (int64_t)a.Le + sk;
-  constexpr int PF = PROT ? 2 : P;  // float4 loads per staged slot
-  float4 rq[PF], re[PF];
-  // counting pass: the block's 64 query rows and 64 candidate rows are each
-  // contiguous, so one buffer descriptor per operand covers them and a row
-  // past nq / E, or a slot past K, reads 0 from the hardware range check (its
-  // offset set to the range's end) — no zero-fill moves and no branches
-  const int64_t rlen = PROT ? 2 * (int64_t)a.K : a.Le;  // floats per staged row
-  // (built in the gather pass too, where no load goes through them)
-  const int64_t nqr = (a.nq - q0 < T) ? a.nq - q0 : T, ner = (a.E - e0 < T) ? a.E - e0 : T;
-  const uint32_t qend = (uint32_t)(nqr * rlen * 4), eend = (uint32_t)((ner > 0 ? ner : 0) * rlen * 4);
-  const auto qrs = buf_rsrc((PROT ? a.qph : a.q) + q0 * rlen, qend);
-  const auto ers = buf_rsrc((PROT ? a.eph : a.ent) + (GATHER ? 0 : e0) * rlen, eend);
-  auto fetch = [&](int k0) {
-    const bool in = (k0 + sk) < a.K;
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      const int64_t o = PROT ? (int64_t)2 * k0 + 4 * p : (int64_t)p * a.K + k0;
-      if constexpr (GATHER) {
-        rq[p] = (in && qrow >= 0) ? *reinterpret_cast<const float4*>(qp + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-        re[p] = (in && erow >= 0) ? *reinterpret_cast<const float4*>(ep + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        const uint32_t off = (uint32_t)((sr * rlen + (PROT ? 2 * sk : sk) + o) * 4);
-        float x[4], y[4];
-        buf_ld4(qrs, in ? off : qend, x);
-        buf_ld4(ers, in ? off : eend, y);
-        rq[p] = make_float4(x[0], x[1], x[2], x[3]);
-        re[p] = make_float4(y[0], y[1], y[2], y[3]);
-      }
-    }
-  };
-  fetch(0);
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = tf2{0.f, 0.f};
-
-  for (int k0 = 0; k0 < a.K; k0 += BK) {
-    if constexpr (CPLX) {
-      const float qr[4] = {rq[0].x, rq[0].y, rq[0].z, rq[0].w}, qi[4] = {rq[1].x, rq[1].y, rq[1].z, rq[1].w};
-      const float er[4] = {re[0].x, re[0].y, re[0].z, re[0].w}, ei[4] = {re[1].x, re[1].y, re[1].z, re[1].w};
-      // (RotatE: candidate sr's re at Es column sr, its im at T + sr;
-      // ComplEx: its (re, im) pair in half (sr / 2) % 2 at (sr / 4)·4 + 2·(sr % 2))
-      const int ec = ((sr & 2) ? T : 0) + (sr >> 2) * 4 + 2 * (sr & 1);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qr[u], qi[u]};
-        if constexpr (M == ROTATE) {
-          Es[sk + u][sr] = er[u];
-          Es[sk + u][T + sr] = ei[u];
-        } else {
-          *reinterpret_cast<tf2*>(&Es[sk + u][ec]) = tf2{er[u], ei[u]};
-        }
-      }
-    } else if constexpr (PROT) {
-      // (sin q, cos q) and (cos e, sin e) of the candidate phase e / (range / π)
-      // (model.py:245-246), evaluated once per element by launch_prot_phase
-      // (Qs: query sr's (sin, cos) at 2·sr; Es: candidate sr's cos at
-      // column sr, its sin at T + sr)
-#pragma unroll
-      for (int u = 0; u < 4; u += 2) {
-        const float4 qv = rq[u >> 1], ev = re[u >> 1];
-        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qv.x, qv.y};
-        *reinterpret_cast<tf2*>(&Qs[sk + u + 1][2 * sr]) = tf2{qv.z, qv.w};
-        Es[sk + u][sr] = ev.x;
-        Es[sk + u][T + sr] = ev.y;
-        Es[sk + u + 1][sr] = ev.z;
-        Es[sk + u + 1][T + sr] = ev.w;
-      }
-    } else if constexpr (SPL) {
-      // TransE: query sr's element as the pair (q, q) at 2·sr
-      const float4 e4 = re[0];
-      *reinterpret_cast<tf2*>(&Qs[sk + 0][2 * sr]) = tf2{rq[0].x, rq[0].x};
-      *reinterpret_cast<tf2*>(&Qs[sk + 1][2 * sr]) = tf2{rq[0].y, rq[0].y};
-      *reinterpret_cast<tf2*>(&Qs[sk + 2][2 * sr]) = tf2{rq[0].z, rq[0].z};
-      *reinterpret_cast<tf2*>(&Qs[sk + 3][2 * sr]) = tf2{rq[0].w, rq[0].w};
-      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
-      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
-    } else {
-      const float4 e4 = re[0];
-      Qs[sk + 0][sr] = rq[0].x; Qs[sk + 1][sr] = rq[0].y;
-      Qs[sk + 2][sr] = rq[0].z; Qs[sk + 3][sr] = rq[0].w;
-      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
-      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
-    }
-    __syncthreads();
-    if (k0 + BK < a.K) fetch(k0 + BK);
-    if constexpr (SPL) {
-      // the next k's LDS operands are read before this k's arithmetic (the
-      // unroll-4 loop waited on every k's reads: lgkmcnt(0) in front of its math)
-      float4 ql[2][2], el[2];
-      auto lds_ld = [&](int k, float4 (&qv)[2], float4& ev) {
-        qv[0] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
-        qv[1] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
-        ev = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-      };
-      lds_ld(0, ql[0], el[0]);
-#pragma unroll
-      for (int k = 0; k < BK; ++k) {
-        if (k + 1 < BK) lds_ld(k + 1, ql[(k + 1) & 1], el[(k + 1) & 1]);
-        TileMath<M, MODE>::transe_spl(ql[k & 1], el[k & 1], acc);
-      }
-    } else
-#pragma unroll 4
-    for (int k = 0; k < BK; ++k) {
-      if constexpr (CPLX || PROT) {
-        const float4 qa = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
-        const float4 qb = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
-        const float4 ea = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-        const float4 eb = *reinterpret_cast<const float4*>(&Es[k][T + tx * 4]);
-        const tf2 q2[4] = {tf2{qa.x, qa.y}, tf2{qa.z, qa.w}, tf2{qb.x, qb.y}, tf2{qb.z, qb.w}};
-        const tf2 e2[4] = {tf2{ea.x, ea.y}, tf2{ea.z, ea.w}, tf2{eb.x, eb.y}, tf2{eb.z, eb.w}};
-        if constexpr (PROT) TileMath<M, MODE>::prot(q2, ea, eb, acc);
-        else if constexpr (M == ROTATE) TileMath<M, MODE>::rot(q2, ea, eb, acc);
-        else TileMath<M, MODE>::cplx(q2, e2, acc);
-      } else {
-        const float4 q4 = *reinterpret_cast<const float4*>(&Qs[k][ty * 4]);
-        const float4 e4 = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-        TileMath<M, MODE>::real(q4, e4, acc, c);
-      }
-    }
-    __syncthreads();
-  }
+#include "kge_tile_reduce.inc"
 }
 
 template <int M, int MODE, bool GATHER, bool SPLT = true>
 __global__ __launch_bounds__(256) void k_rank_tile(TileArgs a) {
-  constexpr bool CPLX = Traits<M>::cplx;
-  constexpr bool PROT = (M == PROTATE);
-  constexpr int P = CPLX ? 2 : 1;             // float4 loads per staged slot
-  constexpr int PS = (CPLX || PROT) ? 2 : 1;  // floats staged per element
-  constexpr int T = TILE_RQ, BK = TILE_BK;
-  // SPL (TransE): the queries are staged pre-splatted, [k][row][q, q], so
-  // each packed operand of the inner loop is a plain register pair (no op_sel
-  // splat, which hipcc materialised with a v_mov for half the pairs).
-  // pRotatE staged the same way, [k][row][sin, sin, cos, cos],
-  // measured slower (whole evaluation 12.89-13.14 vs 12.61-12.68 ms, same box:
-  // twice the query LDS, fewer waves) and keeps the (sin, cos) pairs.
-  constexpr bool SPL = SPLT && (M == TRANSE);
-  constexpr int QW = SPL ? 2 : PS;  // floats per query per k-row of Qs
-  // TransE (SPL) and pRotatE: k-rows padded by 4 floats, so a 16-lane
-  // group's staging stores (4 rows × 4 k-offsets) fall on 16 different banks;
-  // unpadded, the k-offsets' rows are 128 or 64 floats apart, a multiple of
-  // the bank count (4-way conflicts).  pRotatE's tile: SQ_LDS_BANK_CONFLICT
-  // 4.0e8 → 1.4e8 cycles per wn18rr direction, evaluation 12.8-13.1 →
-  // 11.8 ms (`profiles/r06/rank/`).  RotatE measured slower padded (FB15k
-  // 24.4-24.5 → 25.9-26.5 ms) and stays unpadded, as do ComplEx and DistMult.
-  constexpr int PAD = (SPL || PROT) ? 4 : 0;
-  constexpr int QSTR = T * QW + PAD, ESTR = T * PS + PAD;
-  // Qs: [k][row] (real), [k][row][re, im] (complex), or the SPL forms above.
+  using C_ = TileCfg<M, SPLT>;
+  constexpr int T = C_::T, BK = C_::BK;
+  // Qs: [k][row] (real), [k][row][re, im] (complex), or TileCfg's SPL form.
   // Es: [k][row] (real); complex and pRotatE rows in two halves
   // of a k-row, [k][half][row / 4][4] — RotatE: re | im, pRotatE: cos | sin,
   // ComplEx: candidates 4c, 4c+1 | 4c+2, 4c+3 as (re, im) pairs — so the 16
   // candidate columns of a ds_read_b128 lane group are 16 consecutive 16-B
   // slots (every bank once) where [row][8] put columns c and c + 8 on one bank
-  __shared__ __attribute__((aligned(16))) float Qs[BK][QSTR];
-  __shared__ __attribute__((aligned(16))) float Es[BK][ESTR];
+  __shared__ __attribute__((aligned(16))) float Qs[BK][C_::QSTR];
+  __shared__ __attribute__((aligned(16))) float Es[BK][C_::ESTR];
   __shared__ int64_t arow[T], brow[T], tids[T];
   __shared__ float sts[T], sdl[T];
   __shared__ int32_t cnt[T];  // strictly greater beyond the window (≤ 64 per block)
@@ -1803,139 +1655,8 @@ __global__ __launch_bounds__(256) void k_rank_tile(TileArgs a) {
   }
   __syncthreads();
 
-  // staging role: row sr, elements sk .. sk+3 of the slab (K % 4 == 0, so a
-  // float4 is either wholly inside the row or wholly padding; padding terms
-  // are phi(0, 0) = 0 for every model)
-  const int sr = t >> 2, sk = (t & 3) * 4;
-  const int64_t qrow = arow[sr], erow = brow[sr];
-  // pRotatE reads the precomputed phase tables ([row][K][2], 2 float4 per
-  // staged slot); complex rows their re and im halves; real rows one float4
-  const float* qp = PROT ? a.qph + (qrow >= 0 ? qrow : 0) * (int64_t)(2 * a.K) + 2 * sk
-                         : a.q + (qrow >= 0 ? qrow : 0) * (int64_t)a.Le + sk;
-  const float* ep = PROT ? a.eph + (erow >= 0 ? erow : 0) * (int64_t)(2 * a.K) + 2 * sk
-                         : a.ent + (erow >= 0 ? erow : 0) * (int64_t)a.Le + sk;
-  constexpr int PF = PROT ? 2 : P;  // float4 loads per staged slot
-  float4 rq[PF], re[PF];
-  // counting pass: the block's 64 query rows and 64 candidate rows are each
-  // contiguous, so one buffer descriptor per operand covers them and a row
-  // past nq / E, or a slot past K, reads 0 from the hardware range check (its
-  // offset set to the range's end) — no zero-fill moves and no branches
-  const int64_t rlen = PROT ? 2 * (int64_t)a.K : a.Le;  // floats per staged row
-  // (built in the gather pass too, where no load goes through them)
-  const int64_t nqr = (a.nq - q0 < T) ? a.nq - q0 : T, ner = (a.E - e0 < T) ? a.E - e0 : T;
-  const uint32_t qend = (uint32_t)(nqr * rlen * 4), eend = (uint32_t)((ner > 0 ? ner : 0) * rlen * 4);
-  const auto qrs = buf_rsrc((PROT ? a.qph : a.q) + q0 * rlen, qend);
-  const auto ers = buf_rsrc((PROT ? a.eph : a.ent) + (GATHER ? 0 : e0) * rlen, eend);
-  auto fetch = [&](int k0) {
-    const bool in = (k0 + sk) < a.K;
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      const int64_t o = PROT ? (int64_t)2 * k0 + 4 * p : (int64_t)p * a.K + k0;
-      if constexpr (GATHER) {
-        rq[p] = (in && qrow >= 0) ? *reinterpret_cast<const float4*>(qp + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-        re[p] = (in && erow >= 0) ? *reinterpret_cast<const float4*>(ep + o) : make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        const uint32_t off = (uint32_t)((sr * rlen + (PROT ? 2 * sk : sk) + o) * 4);
-        float x[4], y[4];
-        buf_ld4(qrs, in ? off : qend, x);
-        buf_ld4(ers, in ? off : eend, y);
-        rq[p] = make_float4(x[0], x[1], x[2], x[3]);
-        re[p] = make_float4(y[0], y[1], y[2], y[3]);
-      }
-    }
-  };
-  fetch(0);
-
   tf2 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = tf2{0.f, 0.f};
-
-  for (int k0 = 0; k0 < a.K; k0 += BK) {
-    if constexpr (CPLX) {
-      const float qr[4] = {rq[0].x, rq[0].y, rq[0].z, rq[0].w}, qi[4] = {rq[1].x, rq[1].y, rq[1].z, rq[1].w};
-      const float er[4] = {re[0].x, re[0].y, re[0].z, re[0].w}, ei[4] = {re[1].x, re[1].y, re[1].z, re[1].w};
-      // (RotatE: candidate sr's re at Es column sr, its im at T + sr;
-      // ComplEx: its (re, im) pair in half (sr / 2) % 2 at (sr / 4)·4 + 2·(sr % 2))
-      const int ec = ((sr & 2) ? T : 0) + (sr >> 2) * 4 + 2 * (sr & 1);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qr[u], qi[u]};
-        if constexpr (M == ROTATE) {
-          Es[sk + u][sr] = er[u];
-          Es[sk + u][T + sr] = ei[u];
-        } else {
-          *reinterpret_cast<tf2*>(&Es[sk + u][ec]) = tf2{er[u], ei[u]};
-        }
-      }
-    } else if constexpr (PROT) {
-      // (sin q, cos q) and (cos e, sin e) of the candidate phase e / (range / π)
-      // (model.py:245-246), evaluated once per element by launch_prot_phase
-      // (Qs: query sr's (sin, cos) at 2·sr; Es: candidate sr's cos at
-      // column sr, its sin at T + sr)
-#pragma unroll
-      for (int u = 0; u < 4; u += 2) {
-        const float4 qv = rq[u >> 1], ev = re[u >> 1];
-        *reinterpret_cast<tf2*>(&Qs[sk + u][2 * sr]) = tf2{qv.x, qv.y};
-        *reinterpret_cast<tf2*>(&Qs[sk + u + 1][2 * sr]) = tf2{qv.z, qv.w};
-        Es[sk + u][sr] = ev.x;
-        Es[sk + u][T + sr] = ev.y;
-        Es[sk + u + 1][sr] = ev.z;
-        Es[sk + u + 1][T + sr] = ev.w;
-      }
-    } else if constexpr (SPL) {
-      // TransE: query sr's element as the pair (q, q) at 2·sr
-      const float4 e4 = re[0];
-      *reinterpret_cast<tf2*>(&Qs[sk + 0][2 * sr]) = tf2{rq[0].x, rq[0].x};
-      *reinterpret_cast<tf2*>(&Qs[sk + 1][2 * sr]) = tf2{rq[0].y, rq[0].y};
-      *reinterpret_cast<tf2*>(&Qs[sk + 2][2 * sr]) = tf2{rq[0].z, rq[0].z};
-      *reinterpret_cast<tf2*>(&Qs[sk + 3][2 * sr]) = tf2{rq[0].w, rq[0].w};
-      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
-      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
-    } else {
-      const float4 e4 = re[0];
-      Qs[sk + 0][sr] = rq[0].x; Qs[sk + 1][sr] = rq[0].y;
-      Qs[sk + 2][sr] = rq[0].z; Qs[sk + 3][sr] = rq[0].w;
-      Es[sk + 0][sr] = e4.x; Es[sk + 1][sr] = e4.y;
-      Es[sk + 2][sr] = e4.z; Es[sk + 3][sr] = e4.w;
-    }
-    __syncthreads();
-    if (k0 + BK < a.K) fetch(k0 + BK);
-    if constexpr (SPL) {
-      // the next k's LDS operands are read before this k's arithmetic (the
-      // unroll-4 loop waited on every k's reads: lgkmcnt(0) in front of its math)
-      float4 ql[2][2], el[2];
-      auto lds_ld = [&](int k, float4 (&qv)[2], float4& ev) {
-        qv[0] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
-        qv[1] = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
-        ev = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-      };
-      lds_ld(0, ql[0], el[0]);
-#pragma unroll
-      for (int k = 0; k < BK; ++k) {
-        if (k + 1 < BK) lds_ld(k + 1, ql[(k + 1) & 1], el[(k + 1) & 1]);
-        TileMath<M, MODE>::transe_spl(ql[k & 1], el[k & 1], acc);
-      }
-    } else
-#pragma unroll 4
-    for (int k = 0; k < BK; ++k) {
-      if constexpr (CPLX || PROT) {
-        const float4 qa = *reinterpret_cast<const float4*>(&Qs[k][ty * 8]);
-        const float4 qb = *reinterpret_cast<const float4*>(&Qs[k][ty * 8 + 4]);
-        const float4 ea = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-        const float4 eb = *reinterpret_cast<const float4*>(&Es[k][T + tx * 4]);
-        const tf2 q2[4] = {tf2{qa.x, qa.y}, tf2{qa.z, qa.w}, tf2{qb.x, qb.y}, tf2{qb.z, qb.w}};
-        const tf2 e2[4] = {tf2{ea.x, ea.y}, tf2{ea.z, ea.w}, tf2{eb.x, eb.y}, tf2{eb.z, eb.w}};
-        if constexpr (PROT) TileMath<M, MODE>::prot(q2, ea, eb, acc);
-        else if constexpr (M == ROTATE) TileMath<M, MODE>::rot(q2, ea, eb, acc);
-        else TileMath<M, MODE>::cplx(q2, e2, acc);
-      } else {
-        const float4 q4 = *reinterpret_cast<const float4*>(&Qs[k][ty * 4]);
-        const float4 e4 = *reinterpret_cast<const float4*>(&Es[k][tx * 4]);
-        TileMath<M, MODE>::real(q4, e4, acc, c);
-      }
-    }
-    __syncthreads();
-  }
+#include "kge_tile_reduce.inc"
   auto pair_total = [&](int i, int j) -> float { return (j & 1) ? acc[i][j >> 1].y : acc[i][j >> 1].x; };
 
   if (GATHER) {
@@ -1976,24 +1697,16 @@ int launch_rank_tile(int mode, int gather, const TileArgs& a, hipStream_t s) {
   const unsigned gx = gather ? 1u : (unsigned)((a.E + TILE_RQ - 1) / TILE_RQ);
   // KGE_TILE_SPL=0 (diagnostic, same bits): TransE with round 5's staging
   // (op_sel splats, unpadded k-rows, unroll-4 k loop)
-  if (M == TRANSE && env_flag_off("KGE_TILE_SPL")) {
-    if (mode == HEAD_BATCH) {
-      if (gather) hipLaunchKernelGGL((k_rank_tile<M, HEAD_BATCH, true, false>), dim3(gx, gy), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_rank_tile<M, HEAD_BATCH, false, false>), dim3(gx, gy), dim3(256), 0, s, a);
-    } else {
-      if (gather) hipLaunchKernelGGL((k_rank_tile<M, TAIL_BATCH, true, false>), dim3(gx, gy), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_rank_tile<M, TAIL_BATCH, false, false>), dim3(gx, gy), dim3(256), 0, s, a);
-    }
+  const bool spl = !(M == TRANSE && env_flag_off("KGE_TILE_SPL"));
+  auto go = [&](auto kh, auto kt) {
+    hipLaunchKernelGGL(pick_dir(mode, kh, kt), dim3(gx, gy), dim3(256), 0, s, a);
     return (int)hipGetLastError();
-  }
-  if (mode == HEAD_BATCH) {
-    if (gather) hipLaunchKernelGGL((k_rank_tile<M, HEAD_BATCH, true>), dim3(gx, gy), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_rank_tile<M, HEAD_BATCH, false>), dim3(gx, gy), dim3(256), 0, s, a);
-  } else {
-    if (gather) hipLaunchKernelGGL((k_rank_tile<M, TAIL_BATCH, true>), dim3(gx, gy), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_rank_tile<M, TAIL_BATCH, false>), dim3(gx, gy), dim3(256), 0, s, a);
-  }
-  return (int)hipGetLastError();
+  };
+  if (gather)
+    return spl ? go(k_rank_tile<M, HEAD_BATCH, true>, k_rank_tile<M, TAIL_BATCH, true>)
+               : go(k_rank_tile<M, HEAD_BATCH, true, false>, k_rank_tile<M, TAIL_BATCH, true, false>);
+  return spl ? go(k_rank_tile<M, HEAD_BATCH, false>, k_rank_tile<M, TAIL_BATCH, false>)
+             : go(k_rank_tile<M, HEAD_BATCH, false, false>, k_rank_tile<M, TAIL_BATCH, false, false>);
 }
 
 // ------------------------------------------------------- top-k prediction
@@ -2103,7 +1816,7 @@ __global__ __launch_bounds__(256) void k_topk_scan(TopkArgs a) {
     load_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
     float thr = -__builtin_inff();
     for (int64_t e = c0; e < c1; ++e) {
-      if ((bits[e >> 5] >> (e & 31)) & 1u) continue;  // wave-uniform
+      if (filter_bit(bits, e)) continue;  // wave-uniform
       R_ r0;
       load_row<NS, VEC, CPLX>(a.ent + e * a.Le, a.eg, lane, r0);
       const float s0 = Elem<M, MODE>::finish(wave_sum(lane_total<M, MODE, NS, VEC, CPLX>(q, r0, c)), c);
@@ -2225,7 +1938,7 @@ int launch_topk_tile(int mode, const TopkTileArgs& b, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, b);
     return (int)hipGetLastError();
   };
-  return (mode == HEAD_BATCH) ? go(k_topk_tile<M, HEAD_BATCH>) : go(k_topk_tile<M, TAIL_BATCH>);
+  return go(pick_dir(mode, k_topk_tile<M, HEAD_BATCH>, k_topk_tile<M, TAIL_BATCH>));
 }
 
 // ---------------------------------------------- near-tie refinement
@@ -2866,40 +2579,28 @@ int launch_rank_ref(int mode, RefStage stage, const RefArgs& a, hipStream_t s) {
   RefArgs b = a;
   size_t lds = 0;
   unsigned g = (unsigned)((a.nq + 3) / 4);
+  auto launch = [&](auto k, unsigned grid) {
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, b);
+    return (int)hipGetLastError();
+  };
   // (BOTH_DIRS: both directions' queries in one launch, twice the grid)
   auto go = [&](auto kh, auto kt, auto kb) {
-    if (mode == BOTH_DIRS) hipLaunchKernelGGL(kb, dim3(2 * g), dim3(256), lds, s, b);
-    else hipLaunchKernelGGL(mode == HEAD_BATCH ? kh : kt, dim3(g), dim3(256), lds, s, b);
-    return (int)hipGetLastError();
+    return mode == BOTH_DIRS ? launch(kb, 2 * g) : launch(pick_dir(mode, kh, kt), g);
   };
   switch (stage) {
     case RefStage::TrueRef: {
       if (!a.s_true_w) return (int)hipErrorInvalidValue;
       b.ref_global = refine_lp(a.Le) > 1024 ? 1 : 0;
       lds = b.ref_global ? 0 : sizeof(float) * 16 * (size_t)refine_lp(a.Le);
-      const unsigned g4 = (unsigned)((a.nq + 7) / 8);
-      if (mode == BOTH_DIRS)
-        hipLaunchKernelGGL((k_rank_true_ref<M, BOTH_DIRS>), dim3(2 * g4), dim3(256), lds, s, b);
-      else if (mode == HEAD_BATCH)
-        hipLaunchKernelGGL((k_rank_true_ref<M, HEAD_BATCH>), dim3(g4), dim3(256), lds, s, b);
-      else
-        hipLaunchKernelGGL((k_rank_true_ref<M, TAIL_BATCH>), dim3(g4), dim3(256), lds, s, b);
-      return (int)hipGetLastError();
+      g = (unsigned)((a.nq + 7) / 8);  // a half-wave per query
+      return go(k_rank_true_ref<M, HEAD_BATCH>, k_rank_true_ref<M, TAIL_BATCH>, k_rank_true_ref<M, BOTH_DIRS>);
     }
-    case RefStage::SinArgs:
+    case RefStage::SinArgs:  // (a block per query; no both-directions form, as Interval)
       if (M != PROTATE) return (int)hipErrorInvalidValue;
-      if (mode == HEAD_BATCH)
-        hipLaunchKernelGGL((k_rank_sin_args<M, HEAD_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_rank_sin_args<M, TAIL_BATCH>), dim3((unsigned)a.nq), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
+      return launch(pick_dir(mode, k_rank_sin_args<M, HEAD_BATCH>, k_rank_sin_args<M, TAIL_BATCH>), (unsigned)a.nq);
     case RefStage::Interval:
       if (M != PROTATE) return (int)hipErrorInvalidValue;
-      if (mode == HEAD_BATCH)
-        hipLaunchKernelGGL((k_rank_exact_iv<M, HEAD_BATCH>), dim3(g), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_rank_exact_iv<M, TAIL_BATCH>), dim3(g), dim3(256), 0, s, a);
-      return (int)hipGetLastError();
+      return launch(pick_dir(mode, k_rank_exact_iv<M, HEAD_BATCH>, k_rank_exact_iv<M, TAIL_BATCH>), g);
     case RefStage::Window:
       return go(k_rank_window<M, HEAD_BATCH>, k_rank_window<M, TAIL_BATCH>, k_rank_window<M, BOTH_DIRS>);
     case RefStage::Refine: {

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void k_rank_scan_w(RankArgs a) {
   const float* q = a.q + qi * a.Le;
   int gt = 0;
   for (int64_t e = c0; e < c1; ++e) {
-    if ((bits[e >> 5] >> (e & 31)) & 1u) continue;  // wave-uniform
+    if (filter_bit(bits, e)) continue;  // wave-uniform
     const float* er = a.ent + e * a.Le;
     float part = 0.f;
     for (int k = lane; k < S; k += 64) {
