@@ -228,6 +228,49 @@ int kge_train_step(const kge_model_desc *m, int32_t mode, const int64_t *pos, co
                    int32_t *err_flag, void *stream);
 
 /*
+ * LAZY entity Adam: kge_train_step with one difference, for the ENTITY table
+ * only — the update covers the rows the batch touches, so a step's optimizer
+ * traffic follows the batch (at most batch·nneg + 2·batch rows), not the table.
+ *   Touched: a row with at least one in-range occurrence in the batch — a
+ *     positive head, a positive tail or a negative — whether or not its
+ *     gradient is zero.
+ *   A touched row gets exactly kge_train_step's update: the same gradient bits
+ *     (same occurrence order, same arithmetic) and the same per-element Adam,
+ *     with adam->entity.step_size / bias_correction2_sqrt from the optimizer's
+ *     GLOBAL step count (the caller's, as for kge_train_step; no per-row count).
+ *   An untouched row's param, exp_avg and exp_avg_sq are neither read nor
+ *     written (a dense step would decay its moments and move it by them).
+ *   The relation table and the pRotatE modulus keep the dense Adam.
+ * This is "lazy Adam" with this library's per-element update (eps added to
+ * sqrt(exp_avg_sq) / bias_correction2_sqrt); it is NOT torch.optim.SparseAdam's
+ * formula.  From zero moments one lazy step equals one dense step bit for bit
+ * (an untouched row's dense update is p + (-step_size)·(0 / eps)).
+ *   grad_entity is neither read nor written and may be NULL: no dense entity
+ *     gradient exists.  grad_relation follows adam->write_grad as in kge_train_step.
+ *   Single process, whole step: no phases, no entity range, no exchange stage.
+ * Host checks, in kge_train_step's fixed order with the lazy step's own behind
+ * the optimizer descriptor's: adam == NULL (KGE_ERR_ARG); the model; the mode;
+ * grad_relation / losses_out; pos / neg / err_flag / batch / nneg; the adam
+ * descriptor (an entity or relation tensor missing or not the model's own:
+ * KGE_ERR_ARG); regularization != 0 (KGE_ERR_ARG: the L3 gradient is dense);
+ * rows over 2048 floats per (half-)row (KGE_ERR_DIM); 16-byte alignment of the
+ * streamed buffers; subsampling_weight; pRotatE's grad_modulus; the workspace
+ * (KGE_ERR_WORKSPACE); nneg > 8192 (KGE_ERR_DIM).
+ * Workspace: kge_train_lazy_workspace_bytes — kge_train_workspace_bytes plus the
+ * touched-row list and its compaction's scratch.  The list (int32 ids,
+ * ascending) and its length are built on the device behind the occurrence CSR,
+ * O(nentity) integer work at 8 bytes per entity and nothing proportional to
+ * nentity × entity_dim; no allocation, no synchronisation.
+ */
+size_t kge_train_lazy_workspace_bytes(const kge_model_desc *m, int64_t batch, int64_t nneg);
+int kge_train_step_lazy(const kge_model_desc *m, int32_t mode, const int64_t *pos, const int64_t *neg,
+                        int64_t batch, int64_t nneg, const float *subsampling_weight, const float *weight_sum,
+                        int32_t uni_weight, int64_t uni_batch, int32_t adversarial, float adversarial_temperature,
+                        float regularization, const kge_adam_desc *adam, float *grad_entity, float *grad_relation,
+                        float *grad_modulus, float *losses_out, void *workspace, size_t workspace_bytes,
+                        int32_t *err_flag, void *stream);
+
+/*
  * Data-parallel FACTOR EXCHANGE (distributed.py, exchange "factors"): instead
  * of all-reducing the dense [E, entity_dim] gradient, the ranks all-gather the
  * row pass's per-row factors — dL/ds [B, nneg], dL/dq [B, entity_dim] and the

@@ -109,6 +109,12 @@ SIGNATURES = {
         [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _F, C.POINTER(AdamDesc), _P, _P, _P, _P, _P,
          _SZ, _P, _P],
     ),
+    "kge_train_lazy_workspace_bytes": (_SZ, [_DESC, _I64, _I64]),
+    "kge_train_step_lazy": (
+        C.c_int,
+        [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _F, C.POINTER(AdamDesc), _P, _P, _P, _P, _P,
+         _SZ, _P, _P],
+    ),
     "kge_train_rows_slice": (
         C.c_int,
         [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _P, _P, _P, _P, _SZ, _P, _P],

@@ -281,6 +281,30 @@ GradWs carve_grad(void* ws, const kge_model_desc* m, int64_t B, int64_t n, size_
   return w;
 }
 
+// What the lazy step (kge_train_step_lazy) adds behind carve_grad's
+// `grad_bytes`: the touched-row list, at most U = min(E, B·n + 2B) ids, its
+// length, and the compaction's scratch.
+struct LazyWs {
+  int32_t *rows, *nrows;
+  void* sel_tmp;
+  size_t sel_tmp_bytes;
+};
+int64_t lazy_places(const kge_model_desc* m, int64_t B, int64_t n) {
+  const int64_t occ = B * n + 2 * B;
+  return occ < m->nentity ? occ : m->nentity;
+}
+LazyWs carve_lazy(void* ws, const kge_model_desc* m, int64_t B, int64_t n, size_t grad_bytes, size_t* bytes) {
+  Carver c(ws);
+  c.off = grad_bytes;
+  LazyWs w;
+  w.rows = c.take<int32_t>(lazy_places(m, B, n));
+  w.nrows = c.take<int32_t>(4);
+  w.sel_tmp_bytes = touched_rows_temp_bytes(m->nentity);
+  w.sel_tmp = c.take<uint8_t>((int64_t)w.sel_tmp_bytes);
+  *bytes = c.off + 256;
+  return w;
+}
+
 // Data-parallel factor exchange (kge_train_rows_slice / kge_train_step_from_rows)
 // XS_CSR_ONLY: the occurrence CSR of a batch alone, on the caller's stream;
 // XS_FROM_ROWS_CSR: XS_FROM_ROWS with that CSR already in the workspace
@@ -322,6 +346,9 @@ struct StepCall {
   } rows;
   int reg_relations = 1;             // 0: the caller counts the relation rows' regulariser elsewhere
   int64_t csr_lo = 0, csr_hi = -1;   // entity buckets the occurrence CSR builds (-1: to the table's end)
+  // kge_train_step_lazy: the entity pass and its fused Adam cover the batch's
+  // touched rows only; no entity gradient is written (out.entity may be null)
+  bool lazy = false;
 };
 
 // A call's batch as every launch of it sees it.
@@ -335,6 +362,7 @@ struct Batch {
   GradWs w;  // (with the caller's buffers in place of the carved ones where a stage brings its own)
   int32_t* err;
   hipStream_t s;
+  LazyWs lz;  // (lazy step only)
 };
 
 // entity pass variant: column slices (k_entity_sl) when the row fits one
@@ -568,6 +596,11 @@ struct StepPlan {
   // reads (no regulariser partials, no pRotatE modulus update)
   bool fin_wanted, fin_fused;
   float* grad_modulus;  // (pRotatE only)
+  // lazy step: the touched rows are compacted behind the CSR, on its stream,
+  // and the entity launch covers `places` row places (the host-known bound
+  // min(E, B·n + 2B) of the touched rows) in place of the table's E rows
+  bool lazy;
+  int64_t places;
 };
 
 int plan_step(const StepCall& c, const Batch& b, const RowArgs& ra, StepPlan* out) {
@@ -601,6 +634,8 @@ int plan_step(const StepCall& c, const Batch& b, const RowArgs& ra, StepPlan* ou
   p.fin_wanted = (c.phases & KGE_PHASE_FINALIZE) && (c.out.losses || p.grad_modulus);
   p.fin_fused = p.fin_wanted && p.all && p.rel_fused && p.ents.e_end > p.ents.e_begin && !fin_reads_step &&
                 env_int("KGE_FIN_SEPARATE", 0) == 0;
+  p.lazy = c.lazy;
+  p.places = c.lazy ? lazy_places(m, b.B, b.n) : 0;
   *out = p;
   return KGE_OK;
 }
@@ -626,9 +661,13 @@ int rows_phase(const Batch& b, const StepPlan& p, const RowArgs& ra, const CsrAr
   Side* sd = p.sd;
   hipStream_t s = b.s, ss = p.ss;
   int st;
+  auto touched_rows = [&](hipStream_t on) {  // (lazy) behind the CSR, on its stream
+    return launch_status(launch_touched_rows(ca.off, ca.E, b.lz.rows, b.lz.nrows, b.lz.sel_tmp, b.lz.sel_tmp_bytes, on));
+  };
   if (p.csr_serial) {
     st = launch_status(launch_csr(ca, s));
     if (st) return st;
+    if (p.lazy && (st = touched_rows(s))) return st;
   }
   // fork point: the occurrence CSR needs only the batch indices (recorded
   // before anything else is queued, so the side stream never waits for the
@@ -647,6 +686,7 @@ int rows_phase(const Batch& b, const StepPlan& p, const RowArgs& ra, const CsrAr
     if (sd) hipStreamWaitEvent(ss, sd->fork, 0);
     st = launch_status(launch_csr(ca, ss));
     if (st) return st;
+    if (p.lazy && (st = touched_rows(ss))) return st;
     if (sd) hipEventRecord(sd->csr_done, ss);
   }
 
@@ -732,8 +772,15 @@ int run_grad(const StepCall& c, const Batch& b, RowArgs ra, FinArgs fa) {
   }
   fa = fin_args(fa, b, p.ents, reg, p.grad_modulus, c.adam);
   if (c.phases & KGE_PHASE_ENTITY) {
-    const Opt opt = opt_for(c.adam, c.adam ? &c.adam->entity : nullptr);
+    Opt opt = opt_for(c.adam, c.adam ? &c.adam->entity : nullptr);
+    if (p.lazy) opt.write_grad = 0;  // no dense entity gradient exists (the relation's follows write_grad)
     EntArgs ea = ent_args(b, p.ents, (ra.op == ROW_TRAIN) ? b.w.g : ra.g_in, reg, c.out.entity, opt);
+    if (p.lazy) {  // the launch's extent is the row places; the kernels take their rows from rows[]
+      ea.e_begin = 0;
+      ea.e_end = p.places;
+      ea.rows = b.lz.rows;
+      ea.nrows = b.lz.nrows;
+    }
     ea.align_sl = (p.q_slm || p.wide) ? 0
                                       : entity_slice_align(p.ents.nsl, b.geo.eg.S, m->entity_dim, m->entity_embedding,
                                                            opt.write_grad ? c.out.entity : nullptr, ea.adam);
@@ -752,7 +799,7 @@ int run_grad(const StepCall& c, const Batch& b, RowArgs ra, FinArgs fa) {
 // neg: the call's candidates (its negatives, or 'single''s aliased tails); w: its carved workspace
 Batch batch_of(const StepCall& c, const Geom& geo, const Negatives& neg, const GradWs& w) {
   return {c.in.m, geo, kernel_mode(c.in.mode), c.in.pos, neg, c.in.batch, c.in.nneg, w, c.ws.err_flag,
-          as_stream(c.ws.stream)};
+          as_stream(c.ws.stream), LazyWs{}};
 }
 
 int train_impl(const StepCall& c) {
@@ -761,7 +808,7 @@ int train_impl(const StepCall& c) {
   int st = check_model(m, &geo);
   if (st) return st;
   if (c.in.mode != KGE_HEAD_BATCH && c.in.mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  const bool grads_given = c.out.entity && c.out.relation && c.out.losses;
+  const bool grads_given = (c.out.entity || c.lazy) && c.out.relation && c.out.losses;
   const bool rows_given = c.rows.g && c.rows.dq && c.rows.stats;
   if (c.xstage == XS_NONE && !grads_given) return KGE_ERR_ARG;
   const bool csr_only = (c.xstage == XS_CSR_ONLY);
@@ -778,13 +825,24 @@ int train_impl(const StepCall& c) {
       return KGE_ERR_ARG;  // the update is in place on the model's own tables
     if (m->model == KGE_PROTATE && adam->modulus.param && adam->modulus.param != m->modulus) return KGE_ERR_ARG;
   }
-  if (!grad_streams_aligned(geo, c.out.entity, c.out.relation, c.adam)) return KGE_ERR_ARG;
+  if (c.lazy) {
+    // the lazy step's own refusals, behind the optimizer descriptor's (a
+    // missing entity tensor is refused there): a whole single-process step
+    // with its optimizer; no regulariser (its gradient is dense); no wide rows
+    if (!c.adam || c.phases != KGE_PHASE_ALL || c.xstage != XS_NONE || c.e_begin != 0 || c.e_end >= 0)
+      return KGE_ERR_ARG;
+    if (c.loss.regularization != 0.f) return KGE_ERR_ARG;
+    if (geo.ns == 0) return KGE_ERR_DIM;
+  }
+  if (!grad_streams_aligned(geo, c.lazy ? nullptr : c.out.entity, c.out.relation, c.adam)) return KGE_ERR_ARG;
   StepCall::Loss loss = c.loss;
   if (!loss.uni_weight && !loss.subsampling_weight) return KGE_ERR_ARG;
   if (m->model == KGE_PROTATE && !c.out.modulus && c.xstage != XS_ROWS_ONLY && !csr_only) return KGE_ERR_ARG;
   if (exchange && !loss.uni_weight && !loss.weight_sum) return KGE_ERR_ARG;  // the global Σw comes from the caller
   size_t need = 0;
   GradWs w = carve_grad(c.ws.workspace, m, c.in.batch, c.in.nneg, &need);
+  LazyWs lz{};
+  if (c.lazy) lz = carve_lazy(c.ws.workspace, m, c.in.batch, c.in.nneg, need, &need);
   if (!c.ws.workspace || c.ws.bytes < need) return KGE_ERR_WORKSPACE;
   if (exchange) {  // the exchanged per-row factors live in the caller's (gathered) buffers
     w.g = c.rows.g;
@@ -796,7 +854,8 @@ int train_impl(const StepCall& c) {
     wsum_out = w.wsum;  // computed by k_build_q's first block, before k_row reads it
     loss.weight_sum = w.wsum;
   }
-  const Batch b = batch_of(c, geo, {c.in.neg, c.in.nneg}, w);
+  Batch b = batch_of(c, geo, {c.in.neg, c.in.nneg}, w);
+  b.lz = lz;
   RowArgs ra = row_args(b);
   ra.op = ROW_TRAIN;
   ra.adversarial = loss.adversarial ? 1 : 0;
@@ -811,6 +870,9 @@ int train_impl(const StepCall& c) {
   if (c.phases < 1 || c.phases > KGE_PHASE_ALL) return KGE_ERR_ARG;
   const int64_t e_end = c.e_end < 0 ? m->nentity : c.e_end;
   if (c.e_begin < 0 || c.e_begin > e_end || e_end > m->nentity) return KGE_ERR_ARG;
+  // (behind every argument check: rocPRIM's select always needs scratch, so 0 means
+  // its size query failed — no usable device — and nothing can be launched)
+  if (c.lazy && lz.sel_tmp_bytes == 0) return hip_status(hipErrorInvalidDevice);
   return run_grad(c, b, ra, fin_loss(loss, c.in.batch, c.out.losses, c.ws.err_flag));
 }
 
@@ -1541,6 +1603,29 @@ int kge_train_step(const kge_model_desc* m, int32_t mode, const int64_t* pos, co
   c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
   c.adam = adam;
   c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  return train_impl(c);
+}
+
+size_t kge_train_lazy_workspace_bytes(const kge_model_desc* m, int64_t batch, int64_t nneg) {
+  size_t b = 0;
+  carve_grad(nullptr, m, batch, nneg, &b);
+  carve_lazy(nullptr, m, batch, nneg, b, &b);
+  return b;
+}
+
+int kge_train_step_lazy(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg, int64_t batch,
+                        int64_t nneg, const float* subsampling_weight, const float* weight_sum, int32_t uni_weight,
+                        int64_t uni_batch, int32_t adversarial, float adversarial_temperature, float regularization,
+                        const kge_adam_desc* adam, float* grad_entity, float* grad_relation, float* grad_modulus,
+                        float* losses_out, void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  if (!adam) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
+  c.adam = adam;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.lazy = true;
   return train_impl(c);
 }
 

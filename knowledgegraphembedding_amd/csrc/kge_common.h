@@ -77,6 +77,10 @@ int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* st
                       int64_t* ids_out, float* scores_out, hipStream_t s);
 size_t csr_scan_temp_bytes(int64_t nb);
 int launch_csr(const CsrArgs& a, hipStream_t s);
+// the non-empty entity buckets of the CSR offsets `off`, ascending, into rows[0 .. *nrows) (device)
+size_t touched_rows_temp_bytes(int64_t E);
+int launch_touched_rows(const int32_t* off, int64_t E, int32_t* rows, int32_t* nrows, void* tmp, size_t tmp_bytes,
+                        hipStream_t s);
 int launch_rel_rows(const RelArgs& a, hipStream_t s);
 int launch_finalize(const FinArgs& a, hipStream_t s);
 int launch_weight_sum(const float* w, int64_t n, float* out, hipStream_t s);

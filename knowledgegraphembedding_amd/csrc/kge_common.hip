@@ -1,6 +1,8 @@
 // kge_common.hip — model-independent kernels: occurrence CSR (deterministic
 // counting sort), relation-gradient row sums, loss finalisation, Σw and Adam.
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 #include <cstdlib>
 
@@ -204,6 +206,39 @@ int launch_csr(const CsrArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_csr_fill, dim3(gk), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_csr_rank_w, dim3(gb), dim3(256), 0, s, a, nb);
   return (int)hipGetLastError();
+}
+
+// The touched entity rows of a batch (kge_train_step_lazy): the ids of the
+// non-empty entity buckets of the occurrence CSR, ascending, compacted into
+// rows[0 .. *nrows) — rocPRIM's select over the ids 0 .. E-1, 8 bytes of
+// offsets read per entity; scratch from the caller's workspace.  Ids out of
+// range never reach a bucket (k_csr_hist), so none appears here.
+namespace {
+struct BucketNonEmpty {
+  const int32_t* off;
+  __host__ __device__ bool operator()(const int32_t& e) const { return off[e + 1] > off[e]; }
+};
+}  // namespace
+
+size_t touched_rows_temp_bytes(int64_t E) {
+  static thread_local int64_t last_E = -1;
+  static thread_local size_t last_bytes = 0;
+  if (E == last_E) return last_bytes;
+  size_t bytes = 0;
+  if (rocprim::select(nullptr, bytes, rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (int32_t*)nullptr,
+                      (size_t)E, BucketNonEmpty{nullptr}) != hipSuccess)
+    return 0;  // (not remembered: rocPRIM asks the device for its architecture first, so a query made
+               // before a device is usable fails, and the next one must ask again)
+  last_E = E;
+  last_bytes = bytes;
+  return bytes;
+}
+
+int launch_touched_rows(const int32_t* off, int64_t E, int32_t* rows, int32_t* nrows, void* tmp, size_t tmp_bytes,
+                        hipStream_t s) {
+  size_t bytes = tmp_bytes;
+  return (int)rocprim::select(tmp, bytes, rocprim::counting_iterator<int32_t>(0), rows, nrows, (size_t)E,
+                              BucketNonEmpty{off}, s);
 }
 
 int launch_rel_rows(const RelArgs& a, hipStream_t s) {

@@ -154,6 +154,12 @@ struct EntArgs {
   int64_t rel_blocks;
   FinArgs fin;          // fin_fused: the launch's last block runs the loss finalisation
   int fin_fused;        // (only when nothing it reads is written by this launch)
+  // the LAZY instantiations only (kge_train_step_lazy): row place p of the
+  // launch works on entity rows[p], p < *nrows — the batch's touched rows,
+  // ascending, compacted on the device (launch_touched_rows); e_begin / e_end
+  // are not read
+  const int32_t* rows;
+  const int32_t* nrows;
 };
 
 // k_entity_sl's leading blocks: the fused finalisation and the relation rows,

@@ -910,7 +910,11 @@ __global__ __launch_bounds__(256) void k_ship_chain(RowArgs a) {
 // scalar load per occurrence); the entity's own row sits in LDS (zero-padded
 // like q in k_row) so two q rows can be in flight in registers.
 // (3 waves/SIMD: measured, 4 spills and runs slower)
-template <int M, int MODE, int VEC, int NS>
+// LAZY (kge_train_step_lazy): the wave's row is rows[place] of the batch's
+// touched rows instead of e_begin + place; a place at or past *nrows has no row
+// and returns before it reads or writes anything.  Everything after the row is
+// chosen is the dense pass's, so a touched row's bits are too.
+template <int M, int MODE, int VEC, int NS, bool LAZY = false>
 __global__ __launch_bounds__(256, 3) void k_entity(EntArgs a) {
   constexpr bool CPLX = Traits<M>::cplx;
   using R_ = Row<NS, VEC, CPLX>;
@@ -920,8 +924,14 @@ __global__ __launch_bounds__(256, 3) void k_entity(EntArgs a) {
   const int lane = threadIdx.x & 63;
   const int w = wave_id();
   float* es = es_all[w];
-  const int64_t e = a.e_begin + (int64_t)blockIdx.x * 4 + w;
-  if (e >= a.e_end) return;
+  int64_t e = a.e_begin + (int64_t)blockIdx.x * 4 + w;
+  if constexpr (LAZY) {
+    const int64_t place = (int64_t)blockIdx.x * 4 + w;
+    if (place >= (int64_t)a.nrows[0]) return;
+    e = a.rows[place];
+  } else {
+    if (e >= a.e_end) return;
+  }
   Consts c = a.c;
   if constexpr (M == PROTATE) c.modulus = a.modulus[0];
   {
@@ -1079,7 +1089,9 @@ __device__ __forceinline__ void stv_nt(float* __restrict__ p, const float (&x)[4
 // q rows in flight, the moments loaded after the occurrence loop,
 // occurrence buckets filled by k_row in place of the CSR, wave-specialised
 // gather / stream waves.
-template <int M, int MODE, bool QSL = false>
+// LAZY: as in k_entity — the block's entity group addresses rows[] (same block
+// → (slice, group) → XCD mapping, same leading blocks).
+template <int M, int MODE, bool QSL = false, bool LAZY = false>
 __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
   constexpr bool CPLX = Traits<M>::cplx;
   using EL = Elem<M, MODE>;
@@ -1107,8 +1119,14 @@ __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
   }
   const unsigned bx = blockIdx.x - lead;
   const int slice = (int)(bx % (unsigned)nsl);
-  const int64_t e = a.e_begin + (int64_t)(bx / (unsigned)nsl) * 4 + w;
-  if (e >= a.e_end) return;
+  int64_t e = a.e_begin + (int64_t)(bx / (unsigned)nsl) * 4 + w;
+  if constexpr (LAZY) {
+    const int64_t place = (int64_t)(bx / (unsigned)nsl) * 4 + w;
+    if (place >= (int64_t)a.nrows[0]) return;
+    e = a.rows[place];
+  } else {
+    if (e >= a.e_end) return;
+  }
   // this slice's slots [s0, s1) of the (half-)row.  align_sl: the inner
   // boundaries sit on 128-B lines of the row's first half (64-slot slices
   // shifted by the row's 16-B phase sh), so no line of that half is shared by
@@ -2672,8 +2690,15 @@ struct Launch {
   static int entity(const EntArgs& a, hipStream_t s) {
     if constexpr (VEC == 4) {
       if (a.nsl > 0) {
-        const int64_t ne = a.e_end - a.e_begin;
+        const int64_t ne = a.e_end - a.e_begin;  // (lazy: the row places, kge_capi.hip run_grad)
         const unsigned gs = (unsigned)(a.nsl * ((ne + 3) / 4)) + ent_lead_blocks(a);
+        if (a.rows) {
+          if (a.q_sl)
+            hipLaunchKernelGGL((k_entity_sl<M, MODE, true, true>), dim3(gs), dim3(256), 0, s, a);
+          else
+            hipLaunchKernelGGL((k_entity_sl<M, MODE, false, true>), dim3(gs), dim3(256), 0, s, a);
+          return (int)hipGetLastError();
+        }
         if (a.q_sl)
           hipLaunchKernelGGL((k_entity_sl<M, MODE, true>), dim3(gs), dim3(256), 0, s, a);
         else
@@ -2682,6 +2707,10 @@ struct Launch {
       }
     }
     const unsigned grid = (unsigned)((a.e_end - a.e_begin + 3) / 4);
+    if (a.rows) {
+      hipLaunchKernelGGL((k_entity<M, MODE, VEC, NS, true>), dim3(grid), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL((k_entity<M, MODE, VEC, NS>), dim3(grid), dim3(256), 0, s, a);
     return (int)hipGetLastError();
   }

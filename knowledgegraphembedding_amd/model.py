@@ -361,10 +361,37 @@ class KGEModel(nn.Module):
         return self._plugin('pRotatE', head, relation, tail, mode)
 
     # --------------------------------------------------------------- training
-    def _grad_buffers(self):
+    def _check_lazy(self, optimizer, args):
+        """A lazy optimizer (KGELazyAdam) has one step, fused into the gradient
+        passes of a single process; refuse every other configuration before
+        anything is launched.  Returns whether `optimizer` is lazy."""
+        if not getattr(optimizer, 'lazy_entity', False):
+            return False
+        if getattr(self, 'row_partition', None) is not None:
+            raise ValueError("KGELazyAdam (lazy entity Adam) does not run with a row partition")
+        if getattr(args, 'dp_group', None) is not None:
+            raise ValueError("KGELazyAdam (lazy entity Adam) does not run with a data-parallel group")
+        if not self.fuse_optimizer:
+            raise ValueError("KGELazyAdam (lazy entity Adam) exists only fused into the train step: "
+                             "model.fuse_optimizer must be True")
+        if float(args.regularization) != 0.0:
+            raise ValueError("KGELazyAdam (lazy entity Adam) takes no regulariser: the L3 gradient is dense "
+                             "(-r / --regularization must be 0)")
+        return True
+
+    def _grad_buffers(self, lazy=False):
+        """(grad_entity, grad_relation, grad_modulus, losses); a lazy step has
+        no entity gradient, so its buffers hold None in that place."""
         dev = self.entity_embedding.device
         bufs = self._grad_bufs
-        if bufs is None or bufs[0].device != dev or bufs[0].shape != self.entity_embedding.shape:
+        if lazy:
+            if bufs is None or bufs[0] is not None or bufs[1].device != dev \
+                    or bufs[1].shape != self.relation_embedding.shape:
+                gr = torch.empty_like(self.relation_embedding, memory_format=torch.contiguous_format)
+                gm = torch.empty(1, 1, device=dev) if self.model_name == 'pRotatE' else None
+                self._grad_bufs = bufs = (None, gr, gm, torch.empty(5, device=dev))
+            return bufs
+        if bufs is None or bufs[0] is None or bufs[0].device != dev or bufs[0].shape != self.entity_embedding.shape:
             ge = torch.empty_like(self.entity_embedding, memory_format=torch.contiguous_format)
             gr = torch.empty_like(self.relation_embedding, memory_format=torch.contiguous_format)
             gm = torch.empty(1, 1, device=dev) if self.model_name == 'pRotatE' else None
@@ -395,16 +422,25 @@ class KGEModel(nn.Module):
         With `entity_chunks` [(e0, e1), ...] the entity-gradient pass runs one
         row range at a time and `on_entity_chunk(e0, e1, grad_entity)` is called
         as soon as each range is queued (the data-parallel path starts that
-        range's all-reduce there, overlapping the next range's computation)."""
+        range's all-reduce there, overlapping the next range's computation).
+        With a KGELazyAdam `optimizer` the step is kge_train_step_lazy: the
+        entity table's update covers the rows the batch touches, no [E, Le]
+        gradient buffer exists and entity_embedding.grad stays None."""
+        lazy = self._check_lazy(optimizer, args)
+        if lazy and entity_chunks is not None:
+            raise ValueError("KGELazyAdam (lazy entity Adam) takes no entity chunks (a data-parallel path)")
         dev = ops._require_device(self.entity_embedding)
         g, rng = self._host_scalars()
-        ge, gr, gm, losses = self._grad_buffers()
+        ge, gr, gm, losses = self._grad_buffers(lazy)
         if losses_out is not None:  # e.g. a pinned host slot the kernels write directly
             losses = losses_out
         adam = None
         if optimizer is not None and self.fuse_optimizer and hasattr(optimizer, 'prepare_fused'):
             adam = optimizer.prepare_fused(self.entity_embedding, self.relation_embedding, self._modulus(),
                                            write_grad=self.keep_grads)
+        if lazy and adam is None:
+            raise ValueError("KGELazyAdam (lazy entity Adam): the optimizer does not fit the fused step (it must "
+                             "hold the model's own contiguous tables with one betas / eps setting)")
         kw = dict(adversarial=bool(args.negative_adversarial_sampling),
                   temperature=float(getattr(args, 'adversarial_temperature', 1.0)),
                   uni_weight=bool(args.uni_weight), regularization=float(args.regularization),
@@ -413,7 +449,7 @@ class KGEModel(nn.Module):
         desc = self.desc()
         if entity_chunks is None:
             ops.train_step_grads(desc, mode, positive_sample, negative_sample, subsampling_weight, dev, adam=adam,
-                                 **kw)
+                                 lazy=lazy, **kw)
         else:
             run = lambda **x: ops.train_step_grads(desc, mode, positive_sample, negative_sample,  # noqa: E731
                                                    subsampling_weight, dev, **kw, **x)
@@ -423,7 +459,7 @@ class KGEModel(nn.Module):
                 if on_entity_chunk is not None:
                     on_entity_chunk(e0, e1, ge)
             run(phases=_lib.PHASE_FINALIZE)
-        if self.entity_embedding.requires_grad:
+        if self.entity_embedding.requires_grad and not lazy:
             self.entity_embedding.grad = ge
         if self.relation_embedding.requires_grad:
             self.relation_embedding.grad = gr
@@ -443,6 +479,7 @@ class KGEModel(nn.Module):
         False restores the reference's read-back inside the step).
         '''
         model.train()
+        model._check_lazy(optimizer, args)  # (ValueError before a batch is drawn or anything launched)
         optimizer.zero_grad()
         positive_sample, negative_sample, subsampling_weight, mode = next(train_iterator)
         dev = model.entity_embedding.device

@@ -76,11 +76,14 @@ _STATES: dict = {}
 _WS_BYTES: dict = {}  # (dims, counts, B, n) -> kge_train_workspace_bytes
 
 
-def _train_ws_bytes(desc: _lib.ModelDesc, B: int, n: int) -> int:
-    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n)
+def _train_ws_bytes(desc: _lib.ModelDesc, B: int, n: int, lazy: bool = False) -> int:
+    """kge_train_workspace_bytes, or with `lazy` kge_train_lazy_workspace_bytes."""
+    key = (desc.entity_dim, desc.relation_dim, desc.nentity, desc.nrelation, B, n, bool(lazy))
     need = _WS_BYTES.get(key)
     if need is None:
-        need = _WS_BYTES[key] = _lib.load().kge_train_workspace_bytes(desc, B, n)
+        lib = _lib.load()
+        query = lib.kge_train_lazy_workspace_bytes if lazy else lib.kge_train_workspace_bytes
+        need = _WS_BYTES[key] = query(desc, B, n)
     return need
 
 
@@ -205,28 +208,37 @@ def weight_sum(w: torch.Tensor, out: torch.Tensor) -> None:
 
 def train_step_grads(desc: _lib.ModelDesc, mode: str, pos: torch.Tensor, neg: torch.Tensor, sub_w: torch.Tensor,
                      dev, *, adversarial: bool, temperature: float, uni_weight: bool, regularization: float,
-                     grad_entity: torch.Tensor, grad_relation: torch.Tensor, grad_modulus: Optional[torch.Tensor],
+                     grad_entity: Optional[torch.Tensor], grad_relation: torch.Tensor,
+                     grad_modulus: Optional[torch.Tensor],
                      losses: torch.Tensor, weight_sum_dev: Optional[torch.Tensor] = None,
                      uni_batch: int = 0, adam: Optional[_lib.AdamDesc] = None, phases: int = _lib.PHASE_ALL,
-                     entity_range: Optional[tuple] = None) -> None:
+                     entity_range: Optional[tuple] = None, lazy: bool = False) -> None:
     """Fused scoring + loss + backward into the given dense grad buffers (model.py:252-301);
     with `adam`, also the optimizer step, fused into the gradient passes (model.py:303).
     `phases` / `entity_range` run a part of the step (kge_train_step_grads_phased): the
-    data-parallel path reduces entity-row chunks while later chunks are computed."""
+    data-parallel path reduces entity-row chunks while later chunks are computed.
+    `lazy` (with `adam`, whole step only): kge_train_step_lazy — the entity table's Adam
+    covers the rows the batch touches; `grad_entity` is not used and may be None."""
     if mode not in ("head-batch", "tail-batch"):
         raise ValueError("Training batch mode %s not supported" % mode)
+    if lazy and (adam is None or phases != _lib.PHASE_ALL or entity_range is not None):
+        raise ValueError("the lazy train step is a whole step with a fused optimizer (adam=...)")
+    if grad_entity is None and not lazy:
+        raise ValueError("grad_entity is required (only the lazy train step has no entity gradient)")
     pos = _idx(pos, dev)
     neg = _idx(neg, dev)
     w = sub_w.to(dev, dtype=torch.float32, non_blocking=True).contiguous().view(-1)
     B, n = neg.shape
     lib = _lib.load()
     st = state(dev)
-    ws = st.workspace(_train_ws_bytes(desc, B, n))
+    ws = st.workspace(_train_ws_bytes(desc, B, n, lazy))
     common = (desc, _lib.MODE_IDS[mode], pos.data_ptr(), neg.data_ptr(), B, n, w.data_ptr(), _ptr(weight_sum_dev),
               int(bool(uni_weight)), int(uni_batch), int(bool(adversarial)), float(temperature), float(regularization))
-    tail = (grad_entity.data_ptr(), grad_relation.data_ptr(), _ptr(grad_modulus), losses.data_ptr(), ws.data_ptr(),
+    tail = (_ptr(grad_entity), grad_relation.data_ptr(), _ptr(grad_modulus), losses.data_ptr(), ws.data_ptr(),
             ws.numel(), st.err.data_ptr(), _stream(dev))
-    if phases != _lib.PHASE_ALL or entity_range is not None:
+    if lazy:
+        _lib.check(lib.kge_train_step_lazy(*common, adam, *tail), "kge_train_step_lazy")
+    elif phases != _lib.PHASE_ALL or entity_range is not None:
         if adam is not None:
             raise ValueError("phased train steps take no fused optimizer")
         e0, e1 = entity_range if entity_range is not None else (0, desc.nentity)

@@ -1,4 +1,6 @@
-"""KGEAdam — torch.optim.Adam's update as one fused HIP kernel per tensor.
+"""KGEAdam — torch.optim.Adam's update as one fused HIP kernel per tensor;
+KGELazyAdam — the same with the entity table updated only in the rows a batch
+touches.
 
 The reference optimises with a plain torch.optim.Adam(lr) (run.py:266-269,
 re-created on every learning-rate decay, run.py:315-322).  KGEAdam keeps that
@@ -17,6 +19,8 @@ from . import ops
 
 
 class KGEAdam(torch.optim.Optimizer):
+    lazy_entity = False  # KGELazyAdam: the fused step updates touched entity rows only
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
         if weight_decay != 0 or amsgrad:
             raise ValueError("KGEAdam implements the reference's Adam configuration only "
@@ -139,3 +143,24 @@ class KGEAdam(torch.optim.Optimizer):
                 ops.adam_step(p.data, grad, state['exp_avg'], state['exp_avg_sq'], step=step,
                               lr=group['lr'], beta1=beta1, beta2=beta2, eps=group['eps'])
         return loss
+
+
+class KGELazyAdam(KGEAdam):
+    """KGEAdam whose ENTITY table is updated lazily: a fused train step
+    (kge_train_step_lazy) applies Adam only to the entity rows its batch
+    touches — a positive head or tail, or a negative — and neither reads nor
+    writes any other row's parameter or moments.  A touched row gets exactly
+    the dense step's update, with the bias corrections of the optimizer's
+    global step count (there is no per-row count); the relation table and the
+    pRotatE modulus keep the dense update.  This is "lazy Adam" with
+    KGEAdam's own per-element formula, not torch.optim.SparseAdam's.
+
+    Hyper-parameters, state keys and state_dict layout are KGEAdam's, so
+    checkpoints move between the dense and the lazy optimizer in both
+    directions.  The lazy step exists only fused into the gradient passes of a
+    single process: KGEModel.train_step raises ValueError for a row partition,
+    a data-parallel group, model.fuse_optimizer = False or a regulariser.  No
+    dense entity gradient exists, so entity_embedding.grad stays None and
+    step() has nothing left to do for that table."""
+
+    lazy_entity = True

@@ -9,7 +9,8 @@ Differences from the reference, all on the execution side:
   * compute runs on the GPU through libkge_hip.so (there is no CPU path;
     --cuda is implied when a GPU is present and required otherwise);
   * the optimizer is KGEAdam (torch.optim.Adam's update, fused), state-dict
-    compatible with the reference's checkpoints;
+    compatible with the reference's checkpoints (KGE_ENTITY_ADAM=lazy in the
+    environment: KGELazyAdam, which updates only the entity rows a batch touches);
   * under torchrun (WORLD_SIZE > 1) every rank trains on its own -b batch and
     gradients are all-reduced over RCCL (knowledgegraphembedding_amd.distributed);
     rank 0 logs, validates and saves.
@@ -27,7 +28,21 @@ from torch.utils.data import DataLoader
 
 from .dataloader import BidirectionalOneShotIterator, RankShardSampler, TrainDataset
 from .model import KGEModel
-from .optim import KGEAdam
+from .optim import KGEAdam, KGELazyAdam
+
+
+def adam_class():
+    """The optimizer class of a run, from the environment variable
+    KGE_ENTITY_ADAM: "dense" (default) KGEAdam, the reference's dense Adam;
+    "lazy" KGELazyAdam, which updates only the entity rows a batch touches
+    (single GPU, no regulariser — for graphs whose entity table dwarfs a batch).
+    Not a flag: the command line is the reference's."""
+    kind = os.environ.get('KGE_ENTITY_ADAM', 'dense')
+    if kind == 'dense':
+        return KGEAdam
+    if kind == 'lazy':
+        return KGELazyAdam
+    raise ValueError("KGE_ENTITY_ADAM=%s not supported (dense or lazy)" % kind)
 
 
 _FLAG = dict(action='store_true')
@@ -344,7 +359,7 @@ def main(args):
         train_iterator = make_train_iterator(args, train_triples, nentity, nrelation, rank, world)
     if args.do_train:
         current_learning_rate = args.learning_rate
-        optimizer = KGEAdam(trainable(), lr=current_learning_rate)
+        optimizer = adam_class()(trainable(), lr=current_learning_rate)
         warm_up_steps = args.warm_up_steps if args.warm_up_steps else args.max_steps // 2
 
     if args.init_checkpoint:
@@ -388,7 +403,7 @@ def main(args):
             if step >= warm_up_steps:
                 current_learning_rate = current_learning_rate / 10
                 logging.info('Change learning_rate to %f at step %d' % (current_learning_rate, step))
-                optimizer = KGEAdam(trainable(), lr=current_learning_rate)
+                optimizer = adam_class()(trainable(), lr=current_learning_rate)
                 warm_up_steps = warm_up_steps * 3
             if step % args.save_checkpoint_steps == 0:
                 osd = optimizer_state()
