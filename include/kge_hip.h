@@ -582,6 +582,51 @@ int kge_topk(const kge_model_desc *m, int32_t mode, const int64_t *queries, int6
              int32_t *err_flag, void *stream);
 
 /*
+ * Ranks against PER-QUERY CANDIDATE LISTS — the OGB link-prediction protocol
+ * (each test triple ranked against its own fixed list of heads or tails) and
+ * sampled validation (the reference has neither: its users call
+ * KGEModel.forward with the candidates as negatives, model.py:72-164, and
+ * compare the [nq, ncand] scores themselves).
+ *   queries [nq,3] (h,r,t); KGE_HEAD_BATCH ranks h among candidate heads,
+ *   KGE_TAIL_BATCH t among candidate tails.
+ *   cand [nq, ncand] int64, row-major: query q's candidates.  A negative id is
+ *   padding and is skipped (ragged lists are padded with -1).
+ *   ranks_out [nq] int64: 1 + #{j : cand[q,j] >= 0, score(cand[q,j]) > score(true)}.
+ *   ties_out  [nq] int32 (nullable): the same count with ==.
+ *   Nothing else is excluded: there is no filter, and a candidate equal to the
+ *   true id, or a duplicate, counts like any other (a copy of the true id is a
+ *   tie) — what comparing forward's scores gives, and what OGB's evaluator
+ *   combines as 1 + gt + ties / 2.
+ * "score" is the reference's fp32 score on the contract of kge_rank_filtered:
+ * the true entity and every candidate are scored in the mode's reference
+ * operation order (no fast pass) — bit-exact for TransE, DistMult and ComplEx,
+ * for RotatE when m->relation_trig holds the reference's cos / sin (NULL:
+ * correctly rounded on the device), and pRotatE with the correctly rounded
+ * device sin as in the one-call form of kge_rank_filtered (there is no
+ * three-call form here).
+ *   A query with h, r or t out of range sets KGE_DEVERR_INDEX and gets rank 0
+ *   and ties 0; a candidate id >= nentity sets KGE_DEVERR_INDEX and is skipped,
+ *   the rest of its query proceeds.
+ *   Rows of any width and alignment: 16-byte slots or single floats by the
+ *   alignment rule above (relation_trig needs float alignment only); rows too
+ *   wide to stage in LDS are read in place.  Queries go on grid.x: one call
+ *   takes any nq and ncand whose (query, candidate chunk) count stays below
+ *   2^31 — the 65,535-query ceiling of the other ranking calls does not apply.
+ *   The counts are integer sums over the chunks: deterministic, and independent
+ *   of the launch geometry.
+ * Host checks, in this order: the model (as every entry); the mode (KGE_SINGLE:
+ * KGE_ERR_MODE); null queries / cand / ranks_out / err_flag, nq < 0 or
+ * ncand < 1 (KGE_ERR_ARG); nq == 0 returns KGE_OK; more work items than
+ * grid.x holds (KGE_ERR_DIM); the workspace (KGE_ERR_WORKSPACE).
+ * The workspace holds two int32 counters per query (and the queries' q vectors
+ * when rows are read in place) — never an [nq, ncand] score matrix.
+ */
+size_t kge_rank_candidates_workspace_bytes(const kge_model_desc *m, int64_t nq, int64_t ncand);
+int kge_rank_candidates(const kge_model_desc *m, int32_t mode, const int64_t *queries, int64_t nq,
+                        const int64_t *cand, int64_t ncand, int64_t *ranks_out, int32_t *ties_out,
+                        void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/*
  * pRotatE ranks bit-exact to the reference — whose sin (model.py:245) is its
  * CPU vector library's (ATen → MKL VML here), which no device instruction
  * sequence reproduces — in three calls on one stream and workspace:

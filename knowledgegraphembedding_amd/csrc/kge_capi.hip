@@ -1497,6 +1497,74 @@ int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
   return launch_status(launch_topk_merge(w.pscore, w.pid, w.state, nq, parts, k, ids_out, scores_out, s));
 }
 
+// ---- ranking against candidate lists (kge_rank_candidates)
+// The chunks of a query's list: one when the queries alone fill the device
+// (256 CUs × 8 workgroups), else enough to, of at least 64 candidates each and
+// at most CAND_CPC_MAX.  KGE_RANK_CAND_CHUNK (diagnostic): candidates per chunk;
+// the counts are integer sums, so no geometry changes a result.
+int64_t cand_chunks(int64_t nq, int64_t C, int* cpc) {
+  int64_t per = env_int("KGE_RANK_CAND_CHUNK", 0);
+  if (per < 1) {
+    const int64_t want = (2048 + nq - 1) / nq, most = (C + 63) / 64;
+    const int64_t chunks = want < most ? want : most;
+    per = (C + chunks - 1) / chunks;
+  }
+  if (per > CAND_CPC_MAX) per = CAND_CPC_MAX;
+  *cpc = (int)per;
+  return (C + per - 1) / per;
+}
+
+struct CandWs {
+  int32_t *gt, *eq;  // [nq] each, adjacent: one memset
+  float* qref;       // [nq, Le], rows read in place only
+};
+CandWs carve_cand(void* ws, const kge_model_desc* m, int64_t nq, size_t* bytes) {
+  Carver c(ws);
+  CandWs w;
+  w.gt = c.take<int32_t>(2 * nq);
+  w.eq = w.gt ? w.gt + nq : nullptr;
+  w.qref = c.take<float>(cand_slots(m->entity_dim) == 0 ? nq * (int64_t)m->entity_dim : 0);
+  *bytes = c.off + 256;
+  return w;
+}
+
+int rank_cand_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq, const int64_t* cand,
+                   int64_t ncand, int64_t* ranks_out, int32_t* ties_out, void* workspace, size_t workspace_bytes,
+                   int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!queries || !cand || !ranks_out || !err_flag || nq < 0 || ncand < 1) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  int cpc = 0;
+  const int64_t chunks = cand_chunks(nq, ncand, &cpc);
+  if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // (query, chunk) work items on grid.x
+  size_t need = 0;
+  const CandWs w = carve_cand(workspace, m, nq, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  hipStream_t s = as_stream(stream);
+  CandArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
+  a.queries = queries; a.cand = cand; a.nq = nq; a.C = ncand; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  a.c = consts_of(m);
+  a.chunks = chunks; a.cpc = cpc;
+  // 16-byte slots by the header's rule: the row span a multiple of 4, both tables aligned
+  a.vec4 = (a.K % 4 == 0) && aligned16(m->entity_embedding) && aligned16(m->relation_embedding);
+  a.nslot = cand_slots(a.Le);
+  a.in_place = a.nslot == 0;
+  a.qref = w.qref; a.gt = w.gt; a.eq = w.eq; a.err = err_flag;
+  st = hip_status(hipMemsetAsync(w.gt, 0, (size_t)(2 * nq) * sizeof(int32_t), s));
+  if (st) return st;
+  st = launch_status(ops_for(m->model).rank_cand(kernel_mode(mode), a, s));
+  if (st) return st;
+  return launch_status(launch_rank_cand_emit(queries, nq, m->nentity, m->nrelation, w.gt, w.eq, ranks_out, ties_out, s));
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -1961,6 +2029,21 @@ int kge_topk(const kge_model_desc* m, int32_t mode, const int64_t* queries, int6
              void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
   return topk_impl(m, mode, queries, nq, filt_off, filt_ids, k, ids_out, scores_out, path, parts, workspace,
                    workspace_bytes, err_flag, stream);
+}
+
+size_t kge_rank_candidates_workspace_bytes(const kge_model_desc* m, int64_t nq, int64_t ncand) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0 || ncand < 1) return 0;
+  size_t b = 0;
+  carve_cand(nullptr, m, nq, &b);
+  return b;
+}
+
+int kge_rank_candidates(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq,
+                        const int64_t* cand, int64_t ncand, int64_t* ranks_out, int32_t* ties_out, void* workspace,
+                        size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  return rank_cand_impl(m, mode, queries, nq, cand, ncand, ranks_out, ties_out, workspace, workspace_bytes, err_flag,
+                        stream);
 }
 
 int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,

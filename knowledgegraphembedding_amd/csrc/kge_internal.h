@@ -345,6 +345,40 @@ struct TopkTileArgs {
   int32_t* pid;
 };
 
+// Ranking against per-query candidate lists (kge_rank_candidates; k_rank_cand,
+// k_rank_cand_q).  Work unit = (query, chunk of cpc candidates), chunk-minor on
+// grid.x; gt / eq are the workspace's per-query counters, zeroed by the call.
+struct CandArgs {
+  const float* ent;
+  const float* rel;
+  const float* modulus;
+  const float* trig;       // RotatE: [R, 2, Lr] reference cos | sin of the phases, or null
+  const int64_t* queries;  // [nq, 3]
+  const int64_t* cand;     // [nq, C]; negative: padding
+  int64_t nq, C, E, R;
+  int Le, Lr, K;           // K = reduction length (complex: Le / 2)
+  Consts c;
+  int64_t chunks;          // chunks per query
+  int cpc;                 // candidates per chunk (the last one may hold fewer)
+  int vec4;                // rows staged in 16-byte slots (the header's alignment rule)
+  int nslot;               // half-waves with an LDS row slot (cand_slots)
+  int in_place;            // rows too wide for LDS: q from qref, rows read in place
+  float* qref;             // [nq, Le] reference-order q (in_place only; k_rank_cand_q writes it)
+  int32_t* gt;             // [nq] += strictly greater
+  int32_t* eq;             // [nq] += equal
+  int32_t* err;
+};
+constexpr int CAND_CPC_MAX = 1024;  // candidates per chunk: the chunk's scores sit in LDS
+// k_rank_cand's LDS score array, floats: 1 + cpc scores and 2 counters, rounded to 4
+__host__ __device__ inline int cand_scrp(int cpc) { return (cpc + 1 + 2 + 3) & ~3; }
+// half-waves with an LDS row slot: q, the largest score array and the slots
+// (rows rounded to 4 floats) share 64 KB; 0: not even one fits, rows are read in place
+inline int cand_slots(int Le) {
+  const int Lp = (Le + 3) & ~3;
+  const int k = (65536 / 4 - Lp - cand_scrp(CAND_CPC_MAX)) / Lp;
+  return k > 8 ? 8 : (k < 1 ? 0 : k);
+}
+
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {
   Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
@@ -377,6 +411,7 @@ struct ModelOps {
   int (*rank_ref)(int mode, RefStage, const RefArgs&, hipStream_t);
   int (*topk)(int mode, int vec, int ns, const TopkArgs&, hipStream_t);
   int (*topk_tile)(int mode, const TopkTileArgs&, hipStream_t);
+  int (*rank_cand)(int mode, const CandArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

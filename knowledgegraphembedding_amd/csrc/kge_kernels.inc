@@ -2644,6 +2644,266 @@ int launch_rank_ref(int mode, RefStage stage, const RefArgs& a, hipStream_t s) {
   return -1;  // (not a RefStage)
 }
 
+// ------------------------------------- ranking against candidate lists
+// kge_rank_candidates: every query brings its own list cand[q, 0..C) (negative
+// ids: padding) and is ranked among exactly those, in the reference's fp32
+// operation order — k_rank_refine's scoring with the caller's list in place of
+// the fast pass's near-ties, so there is no fast pass, no window and no filter.
+// Work unit = (query, chunk of cpc candidates), one 256-thread block each,
+// chunk-minor on grid.x.  The block builds the query's reference q in LDS
+// (ref_make_q, as k_rank_window), then its half-waves with a row slot walk the
+// items j = half, half + nslot, ...: item 0 is the true entity, items 1..n the
+// chunk's candidates.  A row is staged into the half's LDS slot from registers
+// that were loaded while the previous item was scored (the cascade of
+// ref_score_half reads its elements in a data-dependent order, so it reads LDS).
+// The ids of a half's next 32 items sit one per lane, so a row's address never
+// waits for an id load.  Padding and out-of-range ids score the true row and
+// store NaN, which compares neither greater nor equal: a half-wave's shuffles
+// never diverge.  Scores land in LDS; the block counts them against item 0's
+// and adds its two integers to the query's counters.
+// Dynamic LDS, floats: [q: Lp][scores: 1 + cpc | 2 counters, cand_scrp][slots:
+// nslot × Lp], Lp = refine_lp(Le).  Rows too wide for q and one slot (in_place)
+// are read where they lie and q comes from k_rank_cand_q's global copy
+// (cand_scrp, cand_slots: kge_internal.h).
+
+// the query's reference-order q, element k by thread k mod 256 (k_rank_window's q)
+template <int M, int MODE>
+__device__ __forceinline__ void cand_build_q(const CandArgs& a, int64_t h, int64_t r, int64_t t, const Consts& c,
+                                             float* __restrict__ qo) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  const int64_t x = (MODE == HEAD_BATCH) ? t : h;
+  const float* xr = a.ent + x * a.Le;
+  const float* rr = a.rel + r * a.Lr;
+  const float* tr = (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr;
+  for (int k = threadIdx.x; k < a.K; k += 256) {
+    const float xa = xr[k], xb = CPLX ? xr[a.K + k] : 0.f;
+    const float ra = rr[k], rb = (M == COMPLEX) ? rr[a.K + k] : 0.f;
+    float qa, qb;
+    ref_make_q<M, MODE>(xa, xb, ra, rb, c, qa, qb, tr, k, a.K);
+    qo[k] = qa;
+    if constexpr (CPLX) qo[a.K + k] = qb;
+  }
+}
+
+// TransE over a row staged in the half's own LDS slot: torch.norm(p=1) is one
+// fp32 accumulator over ascending k, which no lane can share — ref_score_half
+// has every lane add the 32 elements of a step from 32 shuffles, one LDS-pipe
+// operation per element, and that pipe, not the gather, bounded the call (85 ms
+// at the 2.5 M-entity shape against a 12 ms gather).  Here the elements
+// |q ∓ e| are written over the row, 32 at a time, and every lane then adds them
+// from 16-byte broadcast reads: the same values in the same order from the
+// same 0, a quarter of the LDS operations.  (Rows read in place keep
+// ref_score_half: global memory is not written.)
+template <int MODE>
+__device__ __forceinline__ float cand_score_transe_lds(const float* __restrict__ q, float* row, int K, const Consts& c,
+                                                       int hl) {
+  for (int k = hl; k < K; k += 32) row[k] = ref_elem<TRANSE, MODE>(q[k], 0.f, row[k], 0.f, c);
+  // the half's lanes read each other's writes: this wave's LDS operations complete in order
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  float acc = 0.f;
+  int k = 0;
+  for (; k + 4 <= K; k += 4) {
+    const tf4 v = *reinterpret_cast<const tf4*>(row + k);  // (slots are 16-byte aligned)
+    acc += v.x;
+    acc += v.y;
+    acc += v.z;
+    acc += v.w;
+  }
+  for (; k < K; ++k) acc += row[k];
+  return ref_finish<TRANSE>(acc, c);
+}
+
+__device__ __forceinline__ bool cand_query_ok(const CandArgs& a, int64_t h, int64_t r, int64_t t) {
+  return h >= 0 && h < a.E && t >= 0 && t < a.E && r >= 0 && r < a.R;
+}
+
+// in_place only: q of every query into the workspace, one block per query
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rank_cand_q(CandArgs a) {
+  const int64_t qi = blockIdx.x;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  if (!cand_query_ok(a, h, r, t)) return;  // (k_rank_cand flags it)
+  cand_build_q<M, MODE>(a, h, r, t, a.c, a.qref + qi * a.Le);
+}
+
+// VW: floats per staging slot — 4 (16-byte loads and LDS writes) or 1.
+// PQ: registers (slots) per lane of the prefetched next row — rows of at most
+// 32·PQ slots; 0: rows staged without prefetch, four loads in flight per lane
+// (as k_rank_refine's wide rows); −1: rows read in place.  Template
+// parameters, so each kernel scores at one place of its text (the half-wave
+// scoring is inlined there, and the prefetched row stays in registers: with
+// the variants chosen at run time inside one kernel it went to scratch).
+template <int VW>
+struct CandSlot { using T = float; };
+template <>
+struct CandSlot<4> { using T = tf4; };  // (a native vector: an array of HIP's float4 struct went to scratch)
+
+template <int M, int MODE, int PQ, int VW>
+__global__ __launch_bounds__(256) void k_rank_cand(CandArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float csm[];
+  constexpr bool IN_PLACE = PQ < 0;
+  using T = typename CandSlot<VW>::T;
+  const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
+  const int64_t qi = (int64_t)blockIdx.x / a.chunks;
+  const int64_t ch = (int64_t)blockIdx.x - qi * a.chunks;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  if (!cand_query_ok(a, h, r, t)) {  // (block-uniform) rank 0, ties 0: k_rank_cand_emit
+    if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+    return;
+  }
+  const int32_t true_e = (int32_t)((MODE == HEAD_BATCH) ? h : t);
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int Le = a.Le, Lp = refine_lp(Le);
+  const int64_t j0 = ch * a.cpc;
+  const int n = (int)((a.C - j0 < a.cpc) ? (a.C - j0) : a.cpc);  // ≥ 1
+  const int items = n + 1;
+  float* scr = csm + (IN_PLACE ? 0 : Lp);
+  int* cnt_s = reinterpret_cast<int*>(scr + a.cpc + 1);
+  float* slots = scr + cand_scrp(a.cpc);
+  if constexpr (!IN_PLACE) cand_build_q<M, MODE>(a, h, r, t, c, csm);
+  const float* qs = IN_PLACE ? a.qref + qi * Le : csm;
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  const int64_t* lst = a.cand + qi * a.C + j0;
+  const int ns = IN_PLACE ? 8 : a.nslot;
+  if (half < ns) {
+    // the half's i-th item is j = half + ns·i; lane hl holds the row id of item
+    // i with i mod 32 = hl of the current group of 32: the true id for item 0
+    // and for a candidate that is not scored (my_ok = 0 then says "discard")
+    int my_e = true_e, my_ok = 1;
+    auto item_id = [&](int i, bool& ok) __attribute__((always_inline)) -> int64_t {  // (i ascending, every i once)
+      if ((i & 31) == 0) {
+        const int j = half + ns * (i + hl);
+        my_e = true_e;
+        my_ok = 1;
+        if (j > 0 && j < items) {
+          const int64_t e = lst[j - 1];
+          my_ok = (e >= 0 && e < a.E);
+          if (my_ok) my_e = (int32_t)e;
+          else if (e >= a.E) atomicOr(a.err, KGE_DEVERR_INDEX);
+        }
+      }
+      const int src = ((tid & 32) + (i & 31)) << 2;
+      ok = __builtin_amdgcn_ds_bpermute(src, my_ok) != 0;
+      return (int64_t)__builtin_amdgcn_ds_bpermute(src, my_e);
+    };
+    auto score_item = [&](int j, float* row, bool ok) __attribute__((always_inline)) {
+      float sc;
+      if constexpr (M == TRANSE && !IN_PLACE) sc = cand_score_transe_lds<MODE>(qs, row, a.K, c, hl);
+      else sc = ref_score_half<M, MODE>(qs, row, a.K, c, hl);
+      if (hl == 0) scr[j] = ok ? sc : NAN;
+      // (the score depends on every element of the row, so the row's reads are
+      // done before the next item overwrites it; the compiler keeps that order)
+      asm volatile("" ::: "memory");
+    };
+    const int nit = (items - half + ns - 1) / ns;  // the half's items (≤ 0: none)
+    if constexpr (IN_PLACE) {
+      for (int i = 0; i < nit; ++i) {
+        bool ok;
+        const int64_t e = item_id(i, ok);
+        score_item(half + ns * i, const_cast<float*>(a.ent + e * Le), ok);  // read in place, never written
+      }
+    } else {
+      float* const row_l = slots + half * Lp;
+      const int nT = Le / VW;
+      T* const rT = reinterpret_cast<T*>(row_l);
+      const T zero = T();
+      if constexpr (PQ > 0) {
+        T nx[PQ > 0 ? PQ : 1];
+        bool nx_ok = true;
+        auto fetch = [&](int i) __attribute__((always_inline)) {
+          const T* sT = reinterpret_cast<const T*>(a.ent + item_id(i, nx_ok) * Le);
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            nx[u] = (k < nT) ? sT[k] : zero;
+          }
+        };
+        if (nit > 0) fetch(0);
+        for (int i = 0; i < nit; ++i) {
+          const bool ok = nx_ok;
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            if (k < nT) rT[k] = nx[u];
+          }
+          if (i + 1 < nit) fetch(i + 1);
+          // the half's 32 lanes read each other's writes: LDS operations of one
+          // wave complete in order, so waiting for this wave's writes suffices
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l, ok);
+        }
+      } else {
+        for (int i = 0; i < nit; ++i) {
+          bool ok;
+          const T* sT = reinterpret_cast<const T*>(a.ent + item_id(i, ok) * Le);
+          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
+            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
+            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
+                    v3 = b3 ? sT[k0 + 96] : zero;
+            rT[k0] = v0;
+            if (b1) rT[k0 + 32] = v1;
+            if (b2) rT[k0 + 64] = v2;
+            if (b3) rT[k0 + 96] = v3;
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l, ok);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const float st = scr[0];
+  int g = 0, e_ = 0;
+  for (int j = 1 + tid; j <= n; j += 256) {
+    g += (scr[j] > st);
+    e_ += (scr[j] == st);
+  }
+  g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
+  e_ = (int)wave_sum((float)e_);
+  if ((tid & 63) == 0 && (g | e_)) {
+    atomicAdd(&cnt_s[0], g);
+    atomicAdd(&cnt_s[1], e_);
+  }
+  __syncthreads();
+  if (tid == 0) {  // integer sums: any order of the chunks gives the same counts
+    if (cnt_s[0]) atomicAdd(&a.gt[qi], cnt_s[0]);
+    if (cnt_s[1]) atomicAdd(&a.eq[qi], cnt_s[1]);
+  }
+}
+
+template <int M>
+int launch_rank_cand(int mode, const CandArgs& a, hipStream_t s) {
+  const int Lp = refine_lp(a.Le);
+  if (a.in_place) {
+    hipLaunchKernelGGL(pick_dir(mode, k_rank_cand_q<M, HEAD_BATCH>, k_rank_cand_q<M, TAIL_BATCH>),
+                       dim3((unsigned)a.nq), dim3(256), 0, s, a);
+    const int st = (int)hipGetLastError();
+    if (st) return st;
+  }
+  const size_t lds = sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (1 + a.nslot)) + cand_scrp(a.cpc));
+  const dim3 grid((unsigned)(a.nq * a.chunks));
+  auto go = [&](auto kh, auto kt) {
+    hipLaunchKernelGGL(pick_dir(mode, kh, kt), grid, dim3(256), lds, s, a);
+    return (int)hipGetLastError();
+  };
+  const int nT = a.vec4 ? a.Le >> 2 : a.Le;  // slots per row
+#define KGE_CAND_GO(PQ_, VW_) go(k_rank_cand<M, HEAD_BATCH, PQ_, VW_>, k_rank_cand<M, TAIL_BATCH, PQ_, VW_>)
+  if (a.in_place) return KGE_CAND_GO(-1, 1);
+  if (a.vec4) {
+    if (nT <= 128) return KGE_CAND_GO(4, 4);
+    if (nT <= 256) return KGE_CAND_GO(8, 4);
+    if (nT <= 512) return KGE_CAND_GO(16, 4);
+    return KGE_CAND_GO(0, 4);
+  }
+  if (nT <= 128) return KGE_CAND_GO(4, 1);
+  if (nT <= 256) return KGE_CAND_GO(8, 1);
+  if (nT <= 512) return KGE_CAND_GO(16, 1);
+  return KGE_CAND_GO(0, 1);
+#undef KGE_CAND_GO
+}
+
 // ------------------------------------------------------------ dispatch
 template <int M, int MODE, int VEC, int NS>
 struct Launch {
@@ -2827,6 +3087,7 @@ struct ModelTable {
     o.rank_ref = &launch_rank_ref<M>;                                                              \
     o.topk = &ModelTable<M>::topk;                                                                 \
     o.topk_tile = &launch_topk_tile<M>;                                                            \
+    o.rank_cand = &launch_rank_cand<M>;                                                            \
     return o;                                                                                      \
   }                                                                                                \
   }

@@ -377,6 +377,19 @@ __global__ __launch_bounds__(256) void k_rank_emit(EmitArgs a) {
   if (a.listed) a.listed[q] = ok ? a.ucnt[q] : 0;
 }
 
+// kge_rank_candidates: rank = 1 + #{strictly greater} from the chunks' summed
+// counts; a query with an id out of range (flagged by k_rank_cand) gets 0 / 0
+__global__ __launch_bounds__(256) void k_rank_cand_emit(const int64_t* queries, int64_t nq, int64_t E, int64_t R,
+                                                        const int32_t* gt, const int32_t* eq, int64_t* ranks,
+                                                        int32_t* ties) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const int64_t h = queries[q * 3], r = queries[q * 3 + 1], t = queries[q * 3 + 2];
+  const bool ok = h >= 0 && h < E && t >= 0 && t < E && r >= 0 && r < R;
+  ranks[q] = ok ? 1 + (int64_t)gt[q] : 0;
+  if (ties) ties[q] = ok ? eq[q] : 0;
+}
+
 
 // --------------------------------------------------------------------------
 // Split-bf16 MFMA tile (path "mfma", the default for DistMult / ComplEx).
@@ -909,6 +922,13 @@ int launch_filter_bits_both(const int64_t* queries, int tab, const int64_t* off_
 
 int launch_rank_emit(const EmitArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_rank_emit, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_rank_cand_emit(const int64_t* queries, int64_t nq, int64_t E, int64_t R, const int32_t* gt,
+                          const int32_t* eq, int64_t* ranks, int32_t* ties, hipStream_t s) {
+  hipLaunchKernelGGL(k_rank_cand_emit, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, queries, nq, E, R, gt, eq,
+                     ranks, ties);
   return (int)hipGetLastError();
 }
 

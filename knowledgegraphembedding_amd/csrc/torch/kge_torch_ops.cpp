@@ -7,6 +7,7 @@
 //   kge::score_backward    its autograd (dense IndexSelectBackward + index_add_)
 //   kge::train_step_grads  train_step up to loss.backward()       model.py:252-301
 //   kge::rank_filtered     test_step's filtered ranking           model.py:383-418
+//   kge::rank_candidates   ranks against per-query candidate lists (no reference counterpart: forward + compare)
 //   kge::topk              top-k link prediction (no reference counterpart: forward + torch.topk)
 //   kge::sample_negatives  TrainDataset.__getitem__ + collate_fn  dataloader.py:34-66
 //   kge::error_flag        the device error flag the kernels OR into (IndexError on read)
@@ -388,6 +389,53 @@ std::tuple<Tensor, Tensor> rank_filtered_meta(const Tensor& entity, const Tensor
           at::empty_symint({queries.sym_size(0)}, o.dtype(at::kInt))};
 }
 
+// ------------------------------------------------- ranking, candidate lists
+// kge_rank_candidates: every query ranked among its own row of cand [nq, C]
+// (negative ids: padding); device sin for pRotatE (no three-call form)
+std::tuple<Tensor, Tensor> rank_candidates_cuda(const Tensor& entity, const Tensor& relation,
+                                                const optional<Tensor>& modulus, const Tensor& queries,
+                                                const Tensor& cand, int64_t mode, int64_t model, double gamma,
+                                                double erange, const optional<Tensor>& relation_trig) {
+  check_model_mode(model, mode, true);
+  const c10::Device dev = require_device({&entity, &relation, modulus ? &*modulus : nullptr, &queries, &cand});
+  c10::DeviceGuard guard(dev);
+  kge_model_desc d = make_desc(model, entity, relation, gamma, erange, modulus);
+  if (relation_trig.has_value() && relation_trig->defined() && model == KGE_ROTATE) {
+    const Tensor& tr = *relation_trig;
+    TORCH_CHECK(tr.device() == dev && tr.scalar_type() == at::kFloat && tr.is_contiguous() && tr.dim() == 3 &&
+                    tr.size(0) == d.nrelation && tr.size(1) == 2 && tr.size(2) == d.relation_dim,
+                "relation_trig: expected a contiguous float32 [", d.nrelation, ", 2, ", d.relation_dim,
+                "] tensor on ", dev);
+    d.relation_trig = tr.data_ptr<float>();
+  }
+  const Tensor q = as_index(queries, dev);
+  TORCH_CHECK(q.dim() == 2 && q.size(1) == 3, "queries must be [nq, 3], got ", q.sizes());
+  const int64_t nq = q.size(0);
+  TORCH_CHECK_VALUE(cand.dim() == 2 && cand.size(0) == nq && cand.size(1) >= 1, "cand must be [nq, C] with nq = ",
+                    nq, " and C >= 1, got ", cand.sizes());
+  const Tensor c = as_index(cand, dev);
+  Tensor ranks = at::empty({nq}, at::TensorOptions().dtype(at::kLong).device(dev));
+  Tensor ties = at::empty({nq}, at::TensorOptions().dtype(at::kInt).device(dev));
+  if (nq == 0) return {ranks, ties};
+  Tensor ws = workspace(kge_rank_candidates_workspace_bytes(&d, nq, c.size(1)), dev);
+  check_status(kge_rank_candidates(&d, (int32_t)mode, q.data_ptr<int64_t>(), nq, c.data_ptr<int64_t>(), c.size(1),
+                                   ranks.data_ptr<int64_t>(), ties.data_ptr<int32_t>(), ws.data_ptr(),
+                                   (size_t)ws.numel(), error_flag_for(dev).data_ptr<int32_t>(), current_stream(dev)),
+               "kge_rank_candidates");
+  return {ranks, ties};
+}
+
+std::tuple<Tensor, Tensor> rank_candidates_meta(const Tensor& entity, const Tensor& relation,
+                                                const optional<Tensor>& modulus, const Tensor& queries,
+                                                const Tensor& cand, int64_t mode, int64_t model, double gamma,
+                                                double erange, const optional<Tensor>& relation_trig) {
+  check_model_mode(model, mode, true);
+  TORCH_CHECK_VALUE(cand.dim() == 2, "cand must be [nq, C], got ", cand.sizes());
+  auto o = queries.options();
+  return {at::empty_symint({queries.sym_size(0)}, o.dtype(at::kLong)),
+          at::empty_symint({queries.sym_size(0)}, o.dtype(at::kInt))};
+}
+
 // -------------------------------------------------------------------- top-k
 // kge_topk with per-query filter lists (filt_off [nq + 1], filt_ids) or none;
 // more than 65535 queries go in several calls
@@ -511,6 +559,12 @@ std::tuple<Tensor, Tensor> rank_filtered_cpu(const Tensor&, const Tensor&, const
   check_model_mode(model, mode, true);
   return refuse_cpu<std::tuple<Tensor, Tensor>>();
 }
+std::tuple<Tensor, Tensor> rank_candidates_cpu(const Tensor&, const Tensor&, const optional<Tensor>&, const Tensor&,
+                                               const Tensor&, int64_t mode, int64_t model, double, double,
+                                               const optional<Tensor>&) {
+  check_model_mode(model, mode, true);
+  return refuse_cpu<std::tuple<Tensor, Tensor>>();
+}
 std::tuple<Tensor, Tensor> topk_cpu(const Tensor&, const Tensor&, const optional<Tensor>&, const Tensor&,
                                     const optional<Tensor>&, const optional<Tensor>&, int64_t mode, int64_t model,
                                     double, double, int64_t, int64_t) {
@@ -536,6 +590,8 @@ TORCH_LIBRARY(kge, m) {
   m.def("rank_filtered(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor filt_off, "
         "Tensor filt_ids, int mode, int model, float gamma, float embedding_range, int path=0, "
         "Tensor? relation_trig=None) -> (Tensor, Tensor)");
+  m.def("rank_candidates(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor cand, int mode, "
+        "int model, float gamma, float embedding_range, Tensor? relation_trig=None) -> (Tensor, Tensor)");
   m.def("topk(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor? filt_off, Tensor? filt_ids, "
         "int mode, int model, float gamma, float embedding_range, int k, int path=0) -> (Tensor, Tensor)");
   m.def("sample_negatives(Tensor triples, Tensor batch, int nentity, int negative_sample_size, Tensor true_off, "
@@ -550,6 +606,7 @@ TORCH_LIBRARY_IMPL(kge, CUDA, m) {
   m.impl("score_backward", &score_backward_cuda);
   m.impl("train_step_grads", &train_step_grads_cuda);
   m.impl("rank_filtered", &rank_filtered_cuda);
+  m.impl("rank_candidates", &rank_candidates_cuda);
   m.impl("topk", &topk_cuda);
   m.impl("sample_negatives", &sample_negatives_cuda);
 }
@@ -559,6 +616,7 @@ TORCH_LIBRARY_IMPL(kge, Meta, m) {
   m.impl("score_backward", &score_backward_meta);
   m.impl("train_step_grads", &train_step_grads_meta);
   m.impl("rank_filtered", &rank_filtered_meta);
+  m.impl("rank_candidates", &rank_candidates_meta);
   m.impl("topk", &topk_meta);
   m.impl("sample_negatives", &sample_negatives_meta);
 }
@@ -568,6 +626,7 @@ TORCH_LIBRARY_IMPL(kge, CPU, m) {
   m.impl("score_backward", &score_backward_cpu);
   m.impl("train_step_grads", &train_step_grads_cpu);
   m.impl("rank_filtered", &rank_filtered_cpu);
+  m.impl("rank_candidates", &rank_candidates_cpu);
   m.impl("topk", &topk_cpu);
   m.impl("sample_negatives", &sample_negatives_cpu);
 }

@@ -30,6 +30,25 @@ from .filters import FilterIndex, triples_array
 _MODELS = ['TransE', 'DistMult', 'ComplEx', 'RotatE', 'pRotatE']
 
 
+def _rank_metrics(ranks_seq):
+    """model.py:405-427: per-query log entries averaged in order — the same
+    left-to-right float sums, without materialising a dict per query."""
+    n = len(ranks_seq)
+    return {
+        'MRR': sum(1.0 / r for r in ranks_seq) / n,
+        'MR': sum(float(r) for r in ranks_seq) / n,
+        'HITS@1': sum(1.0 if r <= 1 else 0.0 for r in ranks_seq) / n,
+        'HITS@3': sum(1.0 if r <= 3 else 0.0 for r in ranks_seq) / n,
+        'HITS@10': sum(1.0 if r <= 10 else 0.0 for r in ranks_seq) / n,
+    }
+
+
+def _check_eval_candidates(n_cand, nentity):
+    if n_cand >= int(nentity):
+        raise ValueError("KGE_EVAL_CANDIDATES = %d: a sampled evaluation draws fewer candidates than the %d "
+                         "entities (unset it for the full filtered ranking)" % (n_cand, int(nentity)))
+
+
 class StepLog(dict):
     """train_step's log — the reference's {name: float} dict (model.py:305-312)
     — filled from the device on first read.
@@ -548,6 +567,20 @@ class KGEModel(nn.Module):
             auc_pr = average_precision_score(y_true, y_score)
             return {'auc_pr': auc_pr}
 
+        n_cand = int(os.environ.get("KGE_EVAL_CANDIDATES", "0") or 0)
+        if n_cand > 0:
+            # sampled evaluation: every query against n_cand drawn candidates
+            _check_eval_candidates(n_cand, model.nentity)  # (before any launch)
+            ranks_seq = []
+            with torch.no_grad():
+                trig = model._rank_rotation(dev)
+                out = [model._rank_candidates_device(q, cand, mode, trig)[0]
+                       for mode, q, cand in model.sampled_eval_blocks(test_triples, all_true_triples, n_cand)]
+                for ranks in out:  # head-batch blocks, then tail-batch
+                    ranks_seq.extend(ranks.cpu().numpy().tolist())
+                ops.raise_on_device_error(dev)
+            return _rank_metrics(ranks_seq)
+
         # Filtered MRR / MR / HITS@{1,3,10}: head-batch queries, then tail-batch
         # (model.py:349-418); the filter is dataloader.py:134-154's.
         index = FilterIndex(all_true_triples, args.nentity, args.nrelation, device=dev)  # built on the GPU
@@ -613,16 +646,81 @@ class KGEModel(nn.Module):
                 ranks_np = torch.cat(ranks_all).cpu().numpy() if ranks_all else np.zeros(0, np.int64)
                 ranks_seq.extend(ranks_np.tolist())
             ops.raise_on_device_error(dev)
-        # model.py:405-427: per-query log entries averaged in order — the same
-        # left-to-right float sums, without materialising a dict per query
-        n = len(ranks_seq)
-        return {
-            'MRR': sum(1.0 / r for r in ranks_seq) / n,
-            'MR': sum(float(r) for r in ranks_seq) / n,
-            'HITS@1': sum(1.0 if r <= 1 else 0.0 for r in ranks_seq) / n,
-            'HITS@3': sum(1.0 if r <= 3 else 0.0 for r in ranks_seq) / n,
-            'HITS@10': sum(1.0 if r <= 10 else 0.0 for r in ranks_seq) / n,
-        }
+        return _rank_metrics(ranks_seq)
+
+    # sampled evaluation (KGE_EVAL_CANDIDATES): queries per sampler / ranking launch
+    EVAL_SAMPLE_BLOCK = 16384
+
+    def sampled_eval_blocks(self, test_triples, all_true_triples, n_cand, seed=None):
+        """The candidate draws of a sampled evaluation (test_step with
+        KGE_EVAL_CANDIDATES=n_cand), one block at a time: yields (mode, queries
+        [b, 3] numpy, candidates [b, n_cand] int64 on the device), the
+        head-batch blocks of EVAL_SAMPLE_BLOCK triples and then the tail-batch
+        ones.  Every query draws n_cand entities uniformly (with replacement)
+        from those that are not a known true answer of it — the true heads of
+        its (r, t) / tails of its (h, r) in `all_true_triples`, the true id
+        among them when the triple is listed there — with the training
+        sampler's kernel (kge_sample_negatives), weights all ones, keyed by
+        sampler.batch_key(seed, block number): `seed` defaults to
+        KGE_EVAL_SEED (else 0), so the same call draws the same candidates."""
+        from . import sampler
+        n_cand = int(n_cand)
+        if n_cand < 1:
+            raise ValueError("sampled evaluation needs at least one candidate")
+        _check_eval_candidates(n_cand, self.nentity)
+        if seed is None:
+            seed = int(os.environ.get("KGE_EVAL_SEED", "0") or 0)
+        dev = ops._require_device(self.entity_embedding)
+        if not getattr(self, '_sampled_eval_logged', False):
+            self._sampled_eval_logged = True
+            logging.info('Evaluation metrics are SAMPLED: every query is ranked against %d drawn candidates '
+                         '(KGE_EVAL_CANDIDATES), not against all %d entities' % (n_cand, int(self.nentity)))
+        triples = triples_array(test_triples)
+        max_draws = max(1 << 20, 1024 * (n_cand + 64))
+        block_no = 0
+        for mode in ('head-batch', 'tail-batch'):
+            for b0 in range(0, len(triples), self.EVAL_SAMPLE_BLOCK):
+                q = np.ascontiguousarray(triples[b0:b0 + self.EVAL_SAMPLE_BLOCK])
+                off, ln, ids = sampler.true_lists_for(all_true_triples, q, mode, self.nentity, self.nrelation)
+                b = len(q)
+                qd = torch.from_numpy(q).to(dev)
+                ids_d = torch.from_numpy(ids).to(dev) if len(ids) else torch.zeros(1, dtype=torch.int64, device=dev)
+                pos = torch.empty(b, 3, dtype=torch.int64, device=dev)
+                cand = torch.empty(b, n_cand, dtype=torch.int64, device=dev)
+                w = torch.empty(b, dtype=torch.float32, device=dev)
+                ops.sample_negatives(qd, torch.arange(b, dtype=torch.int64, device=dev), int(self.nentity), n_cand,
+                                     torch.from_numpy(off).to(dev), torch.from_numpy(ln).to(dev), ids_d,
+                                     torch.ones(b, dtype=torch.float32, device=dev),
+                                     sampler.batch_key(seed, block_no), max_draws, pos, cand, w)
+                block_no += 1
+                yield mode, q, cand
+
+    def _rank_candidates_device(self, queries, cand, mode, trig):
+        return ops.rank_candidates(self.desc(), mode, torch.from_numpy(np.array(queries, dtype=np.int64, order='C')), cand,
+                                   ops._require_device(self.entity_embedding), relation_trig=trig)
+
+    def rank_candidates(self, triples, candidates, mode, relation_trig=None):
+        """Per-query ranks and tie counts (numpy int64, int32) of every (h, r, t)
+        row of `triples` among its own row of `candidates` [nq, C] (an array or
+        a tensor; negative ids are padding): rank = 1 + the candidates that
+        score above the true head ('head-batch') / tail ('tail-batch'), ties =
+        those that score equal, in the reference's fp32 score order
+        (ops.rank_candidates) — the OGB protocol's per-triple candidate lists,
+        whose evaluator combines them as rank + ties / 2.  Nothing is filtered:
+        a candidate equal to the true id is a tie.  RotatE's rotation table
+        defaults per `rank_trig` (see _rank_rotation); pRotatE uses the
+        correctly rounded device sin."""
+        if mode not in ('head-batch', 'tail-batch'):
+            raise ValueError('mode %s not supported' % mode)
+        dev = ops._require_device(self.entity_embedding)
+        q = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+        cand = candidates if isinstance(candidates, torch.Tensor) else \
+            torch.from_numpy(np.array(candidates, dtype=np.int64, order='C'))  # (a copy: the input may be read-only)
+        with torch.no_grad():
+            ranks, ties = self._rank_candidates_device(q, cand, mode, self._rank_rotation(dev, relation_trig))
+        res = ranks.cpu().numpy(), ties.cpu().numpy()
+        ops.raise_on_device_error(dev)
+        return res
 
     def rank_queries_both(self, triples, all_true_triples, path="auto", relation_trig=None):
         """rank_queries for head-batch and tail-batch, both queued before the

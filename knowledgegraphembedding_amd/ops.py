@@ -555,6 +555,47 @@ def rank_filtered_both(desc: _lib.ModelDesc, queries: torch.Tensor, filt_head, f
     return (ranks, ties, lst) if listed else (ranks, ties)
 
 
+def rank_candidates(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, cand: torch.Tensor, dev,
+                    relation_trig: Optional[torch.Tensor] = None):
+    """Ranks (int64) and tie counts (int32) of every query among its own row of
+    `cand` [nq, C] (kge_rank_candidates), as device tensors: rank = 1 + the
+    candidates scoring above the true entity, ties = those scoring equal, both
+    in the reference's fp32 score order.  A negative id is padding; nothing
+    else is excluded (a copy of the true id is a tie).  mode "head-batch" ranks
+    h among candidate heads, "tail-batch" t among candidate tails.
+    `relation_trig` as for rank_filtered.  The device error flag is left for
+    the caller's next read (raise_on_device_error): a query with an id out of
+    range has rank 0 and ties 0, a candidate id ≥ nentity is skipped."""
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("mode %s not supported" % mode)
+    if relation_trig is not None:
+        shape = (desc.nrelation, 2, desc.relation_dim)
+        if (tuple(relation_trig.shape) != shape or relation_trig.dtype != torch.float32
+                or not relation_trig.is_contiguous() or relation_trig.device != dev):
+            raise ValueError(f"relation_trig: expected a contiguous float32 {shape} tensor on {dev}")
+        desc = _lib.ModelDesc.from_buffer_copy(desc)
+        desc.relation_trig = relation_trig.data_ptr()
+    q = _idx(queries, dev)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"queries: {tuple(q.shape)}, expected [nq, 3]")
+    nq = q.shape[0]
+    if cand.dim() != 2 or cand.shape[0] != nq or cand.shape[1] < 1:
+        raise ValueError(f"cand: {tuple(cand.shape)}, expected [{nq}, C] with C >= 1")
+    cd = _idx(cand, dev)
+    C = cd.shape[1]
+    ranks = torch.empty(nq, dtype=torch.int64, device=dev)
+    ties = torch.empty(nq, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    st = state(dev)
+    ws = st.workspace(lib.kge_rank_candidates_workspace_bytes(desc, nq, C))  # (clears rank_ws_ptr: the table buffers go)
+    _lib.check(
+        lib.kge_rank_candidates(desc, _lib.MODE_IDS[mode], q.data_ptr(), nq, cd.data_ptr(), C, ranks.data_ptr(),
+                                ties.data_ptr(), ws.data_ptr(), ws.numel(), st.err.data_ptr(), _stream(dev)),
+        "kge_rank_candidates",
+    )
+    return ranks, ties
+
+
 TOPK_MAX_K = 128  # kge_hip.h KGE_TOPK_MAX_K
 TOPK_PATHS = {"auto": 0, "tile": 2, "scan": 3}
 

@@ -49,15 +49,41 @@ def batch_key(seed: int, batch_no: int) -> int:
     return _mix64(_mix64(seed) + batch_no * _WEYL)
 
 
-def _group_lists(key: np.ndarray, member: np.ndarray, span: int):
-    """Sorted unique members per key; per-row (offset, length) into the id array."""
+def _lookup_lists(key: np.ndarray, member: np.ndarray, span: int, qkey: np.ndarray):
+    """Sorted unique members per key; (offset, length) into the id array for every
+    row of `qkey` (a key that does not occur: an empty list)."""
     pair = np.unique(key * span + member)
     gkey = pair // span
     ids = (pair - gkey * span).astype(np.int64)
     ukey, start = np.unique(gkey, return_index=True)
     length = np.diff(np.append(start, len(pair)))
-    slot = np.searchsorted(ukey, key)
-    return start[slot].astype(np.int64), length[slot].astype(np.int32), ids
+    if len(ukey) == 0:
+        return np.zeros(len(qkey), np.int64), np.zeros(len(qkey), np.int32), ids
+    slot = np.minimum(np.searchsorted(ukey, qkey), len(ukey) - 1)
+    hit = ukey[slot] == qkey
+    return (np.where(hit, start[slot], 0).astype(np.int64), np.where(hit, length[slot], 0).astype(np.int32), ids)
+
+
+def _group_lists(key: np.ndarray, member: np.ndarray, span: int):
+    """Sorted unique members per key; per-row (offset, length) into the id array."""
+    return _lookup_lists(key, member, span, key)
+
+
+def true_lists_for(all_true_triples, queries, mode: str, nentity: int, nrelation: int):
+    """kge_sample_negatives' true lists for `queries` [n, 3], taken from
+    `all_true_triples`: per query (offset, length) into the sorted ids of the true
+    heads of its (r, t) (head-batch) or true tails of its (h, r) (tail-batch) —
+    TrueLists' grouping, looked up per query instead of per listed triple."""
+    tr = np.asarray(all_true_triples, dtype=np.int64).reshape(-1, 3)
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    E, R = int(nentity), int(nrelation)
+    if R * E * E >= 2 ** 62:
+        raise ValueError("entity/relation counts too large for the packed (key, member) sort")
+    if mode == 'head-batch':
+        return _lookup_lists(tr[:, 1] * E + tr[:, 2], tr[:, 0], E, q[:, 1] * E + q[:, 2])
+    if mode == 'tail-batch':
+        return _lookup_lists(tr[:, 0] * R + tr[:, 1], tr[:, 2], E, q[:, 0] * R + q[:, 1])
+    raise ValueError('negative batch mode %s not supported' % mode)
 
 
 class TrueLists:

@@ -17,6 +17,9 @@ same library with no Python in the call path:
                        Tensor filt_off, Tensor filt_ids, int mode, int model, float gamma,
                        float embedding_range, int path=0, Tensor? relation_trig=None)
                        -> (Tensor, Tensor)
+    kge::rank_candidates(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries,
+                         Tensor cand, int mode, int model, float gamma, float embedding_range,
+                         Tensor? relation_trig=None) -> (Tensor, Tensor)
     kge::sample_negatives(..., Tensor(a!) pos_out, Tensor(b!) neg_out, Tensor(c!) w_out) -> ()
     kge::error_flag(Device device) -> Tensor
 
