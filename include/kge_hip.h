@@ -627,6 +627,55 @@ int kge_rank_candidates(const kge_model_desc *m, int32_t mode, const int64_t *qu
                         void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /*
+ * RELATION PREDICTION — "which relation holds between h and t?": every query
+ * (h, r, t) of queries [nq,3] is scored with every relation r' in
+ * [0, nrelation), and its own r is ranked among them (the reference has no such
+ * call: its users flatten nq × R triples through KGEModel.forward(mode='single')).
+ * "score" is the reference's fp32 score of the triple (h, r', t) in 'single'
+ * mode — (h + r') − t, (h * r') * t, the non-head-batch branch of
+ * model.py:166-249, reduced by ATen's sum(dim=2) / norm(p=1) — on the contract
+ * of kge_rank_candidates: bit-exact for TransE, DistMult and ComplEx, for RotatE
+ * when m->relation_trig holds the reference's cos / sin (NULL: correctly rounded
+ * on the device, evaluated once per relation into a table in the workspace),
+ * and pRotatE with the correctly rounded device sin — its sin acts on the
+ * phase sum (h + r') − t, so no table can carry it and it is evaluated per
+ * (query, relation, element); there is no three-call form here.
+ *   filt_off [nq + 1] / filt_ids: per-query lists of relation ids to exclude —
+ *   the other relations r' with (h, r', t) a known true triple; both NULL: no
+ *   filter.  Listing the true r, an id twice or an id outside [0, nrelation)
+ *   is harmless and no error.
+ *   ranks_out [nq] int64: 1 + #{r' != r, r' not excluded : score(r') > score(r)}.
+ *   ties_out  [nq] int32 (nullable): the same count with ==.  The true relation
+ *   is never counted against itself (as kge_rank_filtered, unlike
+ *   kge_rank_candidates).
+ *   scores_out [nq, nrelation] float (nullable): the score of every relation,
+ *   excluded ones included — the only [nq, nrelation] object of the call, and
+ *   the caller's; the workspace never holds one.
+ *   r == -1 means "no true relation" (prediction): rank 0, ties 0, the scores
+ *   are written, no error.  Any other r outside [0, nrelation), or an h or t
+ *   outside [0, nentity), sets KGE_DEVERR_INDEX and gives that query rank 0,
+ *   ties 0 and a NaN row of scores_out; the other queries proceed.
+ *   Rows of any width and alignment: 16-byte slots or single floats by the
+ *   alignment rule above (RotatE: of the entity table and the trig table);
+ *   rows too wide to stage h, t and one relation row in LDS are read in place.
+ *   The counts are integer sums over chunks of the relation range:
+ *   deterministic, and independent of the launch geometry.  Queries go on
+ *   grid.x: the 65,535-query ceiling of the other ranking calls does not apply.
+ * Host checks, in this order: the model (as every entry); null queries /
+ * ranks_out / err_flag (KGE_ERR_ARG); nq < 0 (KGE_ERR_ARG); filt_off and
+ * filt_ids not both NULL or both set (KGE_ERR_ARG); nq == 0 returns KGE_OK;
+ * more (query, relation chunk) work items than grid.x holds (KGE_ERR_DIM); the
+ * workspace (KGE_ERR_WORKSPACE).  There is no mode argument.
+ * The workspace holds two int32 counters per query, and RotatE's
+ * [nrelation, 2, relation_dim] table when relation_trig is NULL.
+ */
+size_t kge_rank_relations_workspace_bytes(const kge_model_desc *m, int64_t nq);
+int kge_rank_relations(const kge_model_desc *m, const int64_t *queries, int64_t nq,
+                       const int64_t *filt_off, const int64_t *filt_ids,
+                       int64_t *ranks_out, int32_t *ties_out, float *scores_out,
+                       void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/*
  * pRotatE ranks bit-exact to the reference — whose sin (model.py:245) is its
  * CPU vector library's (ATen → MKL VML here), which no device instruction
  * sequence reproduces — in three calls on one stream and workspace:

@@ -153,6 +153,8 @@ SIGNATURES = {
     "kge_topk": (C.c_int, [_DESC, _I32, _P, _I64, _P, _P, _I32, _P, _P, _I32, _I32, _P, _SZ, _P, _P]),
     "kge_rank_candidates_workspace_bytes": (_SZ, [_DESC, _I64, _I64]),
     "kge_rank_candidates": (C.c_int, [_DESC, _I32, _P, _I64, _P, _I64, _P, _P, _P, _SZ, _P, _P]),
+    "kge_rank_relations_workspace_bytes": (_SZ, [_DESC, _I64]),
+    "kge_rank_relations": (C.c_int, [_DESC, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_sin_args": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_finish_sin": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_stage_timer": (C.c_int, [_I32, _P, _I32]),

@@ -1565,6 +1565,90 @@ int rank_cand_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries
   return launch_status(launch_rank_cand_emit(queries, nq, m->nentity, m->nrelation, w.gt, w.eq, ranks_out, ties_out, s));
 }
 
+// ---- relation prediction (kge_rank_relations)
+// The chunks of the relation range: all of R in one (up to REL_CPC_MAX) when
+// the queries alone fill the device (256 CUs × 8 workgroups), else enough to,
+// of at least 64 relations each; chunks of equal size (R = 1345 is 673 + 672,
+// not 1024 + 321: every chunk stages h and t once more).  KGE_RANK_REL_CHUNK
+// (diagnostic): relations per chunk; the counts are integer sums, so no
+// geometry changes a result.
+int64_t rel_chunks(int64_t nq, int64_t R, int* cpc) {
+  int64_t per = env_int("KGE_RANK_REL_CHUNK", 0);
+  if (per < 1) {
+    const int64_t want = (2048 + nq - 1) / nq, most = (R + 63) / 64, least = (R + REL_CPC_MAX - 1) / REL_CPC_MAX;
+    int64_t chunks = want < most ? want : most;
+    if (chunks < least) chunks = least;
+    per = (R + chunks - 1) / chunks;
+  }
+  if (per > REL_CPC_MAX) per = REL_CPC_MAX;
+  *cpc = (int)per;
+  return (R + per - 1) / per;
+}
+
+struct RelWs {
+  int32_t *gt, *eq;  // [nq] each, adjacent: one memset
+  float* trig;       // [R, 2, Lr], RotatE without a caller's table only
+};
+RelWs carve_rel(void* ws, const kge_model_desc* m, int64_t nq, size_t* bytes) {
+  Carver c(ws);
+  RelWs w;
+  w.gt = c.take<int32_t>(2 * nq);
+  w.eq = w.gt ? w.gt + nq : nullptr;
+  const bool table = m->model == KGE_ROTATE && !m->relation_trig;
+  w.trig = c.take<float>(table ? (size_t)m->nrelation * 2 * (size_t)m->relation_dim : 0);
+  *bytes = c.off + 256;
+  return w;
+}
+
+int rank_rel_impl(const kge_model_desc* m, const int64_t* queries, int64_t nq, const int64_t* filt_off,
+                  const int64_t* filt_ids, int64_t* ranks_out, int32_t* ties_out, float* scores_out, void* workspace,
+                  size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (!queries || !ranks_out || !err_flag) return KGE_ERR_ARG;
+  if (nq < 0) return KGE_ERR_ARG;
+  if ((filt_off == nullptr) != (filt_ids == nullptr)) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  int cpc = 0;
+  const int64_t chunks = rel_chunks(nq, m->nrelation, &cpc);
+  if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // (query, chunk) work items on grid.x
+  size_t need = 0;
+  const RelWs w = carve_rel(workspace, m, nq, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  hipStream_t s = as_stream(stream);
+  RelRankArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.queries = queries; a.filt_off = filt_off; a.filt_ids = filt_ids;
+  a.nq = nq; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  a.c = consts_of(m);
+  a.chunks = chunks; a.cpc = cpc;
+  if (m->model == KGE_ROTATE) {
+    a.trig = m->relation_trig;
+    if (!a.trig) {
+      st = launch_status(launch_rel_trig_table(m->relation_embedding, m->nrelation, m->relation_dim, a.c.kappa, w.trig, s));
+      if (st) return st;
+      a.trig = w.trig;
+    }
+  }
+  // 16-byte slots: the row span a multiple of 4, the entity table and the table
+  // the relation rows come from (RotatE: the trig table) aligned
+  a.vec4 = (a.K % 4 == 0) && aligned16(m->entity_embedding) &&
+           aligned16(m->model == KGE_ROTATE ? a.trig : m->relation_embedding);
+  a.nslot = rel_slots(a.Le);
+  a.in_place = a.nslot == 0;
+  a.scores = scores_out; a.gt = w.gt; a.eq = w.eq; a.err = err_flag;
+  st = hip_status(hipMemsetAsync(w.gt, 0, (size_t)(2 * nq) * sizeof(int32_t), s));
+  if (st) return st;
+  st = launch_status(ops_for(m->model).rank_rel(a, s));
+  if (st) return st;
+  // (r = -1 is "not in [0, R)" to the emit kernel: rank 0, ties 0)
+  return launch_status(launch_rank_cand_emit(queries, nq, m->nentity, m->nrelation, w.gt, w.eq, ranks_out, ties_out, s));
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -2044,6 +2128,21 @@ int kge_rank_candidates(const kge_model_desc* m, int32_t mode, const int64_t* qu
                         size_t workspace_bytes, int32_t* err_flag, void* stream) {
   return rank_cand_impl(m, mode, queries, nq, cand, ncand, ranks_out, ties_out, workspace, workspace_bytes, err_flag,
                         stream);
+}
+
+size_t kge_rank_relations_workspace_bytes(const kge_model_desc* m, int64_t nq) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0) return 0;
+  size_t b = 0;
+  carve_rel(nullptr, m, nq, &b);
+  return b;
+}
+
+int kge_rank_relations(const kge_model_desc* m, const int64_t* queries, int64_t nq, const int64_t* filt_off,
+                       const int64_t* filt_ids, int64_t* ranks_out, int32_t* ties_out, float* scores_out,
+                       void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  return rank_rel_impl(m, queries, nq, filt_off, filt_ids, ranks_out, ties_out, scores_out, workspace, workspace_bytes,
+                       err_flag, stream);
 }
 
 int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,

@@ -75,6 +75,8 @@ int launch_rank_emit(const EmitArgs& a, hipStream_t s);
 // kge_rank_candidates: ranks / ties (nullable) from the per-query counts (kge_rank_mfma.hip)
 int launch_rank_cand_emit(const int64_t* queries, int64_t nq, int64_t E, int64_t R, const int32_t* gt,
                           const int32_t* eq, int64_t* ranks, int32_t* ties, hipStream_t s);
+// kge_rank_relations: RotatE's [R, 2, Lr] correctly rounded cos | sin table (kge_rank_mfma.hip)
+int launch_rel_trig_table(const float* rel, int64_t R, int Lr, float kappa, float* out, hipStream_t s);
 // kge_topk's reduction of every query's `parts` partial lists (kge_common.hip)
 int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
                       int64_t* ids_out, float* scores_out, hipStream_t s);

@@ -379,6 +379,44 @@ inline int cand_slots(int Le) {
   return k > 8 ? 8 : (k < 1 ? 0 : k);
 }
 
+// Relation prediction (kge_rank_relations; k_rank_rel).  Work unit = (query,
+// chunk of cpc consecutive relations), chunk-minor on grid.x; gt / eq are the
+// workspace's per-query counters, zeroed by the call.
+struct RelRankArgs {
+  const float* ent;
+  const float* rel;
+  const float* modulus;
+  const float* trig;        // RotatE: [R, 2, Lr] cos | sin of the phases (the caller's, or the workspace's)
+  const int64_t* queries;   // [nq, 3]; r = -1: no true relation (scores only)
+  const int64_t* filt_off;  // [nq + 1] or null: no filter
+  const int64_t* filt_ids;  // relation ids excluded per query
+  int64_t nq, E, R;
+  int Le, Lr, K;            // K = reduction length (complex: Le / 2)
+  Consts c;
+  int64_t chunks;           // chunks per query
+  int cpc;                  // relations per chunk (the last one may hold fewer)
+  int vec4;                 // rows staged in 16-byte slots
+  int nslot;                // half-waves with an LDS row slot (rel_slots)
+  int in_place;             // rows too wide for LDS: h, t and the relation rows read in place
+  float* scores;            // [nq, R] or null
+  int32_t* gt;              // [nq] += strictly greater
+  int32_t* eq;              // [nq] += equal
+  int32_t* err;
+};
+constexpr int REL_CPC_MAX = 1024;  // relations per chunk: the chunk's scores sit in LDS
+// k_rank_rel's LDS score array, floats: 1 + cpc scores and 2 counters, rounded to 4
+__host__ __device__ inline int rel_scrp(int cpc) { return (cpc + 1 + 2 + 3) & ~3; }
+// ... and its filter bitmap of cpc bits, 32-bit words rounded to 4
+__host__ __device__ inline int rel_bmw(int cpc) { return (((cpc + 31) >> 5) + 3) & ~3; }
+// half-waves with an LDS row slot: the h and t rows, the largest score array
+// and bitmap and the slots (rows rounded to 4 floats) share 64 KB; 0: not even
+// one slot fits, every row is read in place
+inline int rel_slots(int Le) {
+  const int Lp = (Le + 3) & ~3;
+  const int k = (65536 / 4 - 2 * Lp - rel_scrp(REL_CPC_MAX) - rel_bmw(REL_CPC_MAX)) / Lp;
+  return k > 8 ? 8 : (k < 1 ? 0 : k);
+}
+
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {
   Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
@@ -412,6 +450,7 @@ struct ModelOps {
   int (*topk)(int mode, int vec, int ns, const TopkArgs&, hipStream_t);
   int (*topk_tile)(int mode, const TopkTileArgs&, hipStream_t);
   int (*rank_cand)(int mode, const CandArgs&, hipStream_t);
+  int (*rank_rel)(const RelRankArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

@@ -2904,6 +2904,269 @@ int launch_rank_cand(int mode, const CandArgs& a, hipStream_t s) {
 #undef KGE_CAND_GO
 }
 
+// ------------------------------------------------- relation prediction
+// kge_rank_relations: query (h, r, t) is scored with every relation r' in
+// [0, R) — k_rank_cand with the roles turned round: the two entity rows are
+// fixed per query, the relation rows are the ones walked.  Work unit = (query,
+// chunk of cpc consecutive relations), one 256-thread block each, chunk-minor
+// on grid.x.  The block stages the query's h row and t row in LDS once; its
+// half-waves with a row slot walk the items j = half, half + nslot, ...: item 0
+// is the true relation (relation 0 when r = −1: its score is never compared),
+// items 1..n the relations j0 .. j0 + n − 1.  A relation row — RotatE: its
+// [cos | sin] row of the trig table, the caller's or the one k_rel_trig_table
+// built in the workspace — is staged into the half's LDS slot from registers
+// loaded while the previous item was scored.  Element k is ref_elem<M, TAIL>(
+// ref_make_q<M, TAIL>(h_k, r'_k), t_k): 'single' mode is the tail-batch
+// association (model.py:166-249), reduced by ref_cascade_half, or for TransE
+// by the sequential sum over the elements written back over the slot
+// (cand_score_transe_lds's trick).  Scores land in LDS; the ids of the query's
+// filter list that fall into the chunk are marked in a bitmap of cpc bits; the
+// block counts the unmarked relations other than r against item 0, adds its two
+// integers to the query's counters and writes its slice of scores_out.
+// Dynamic LDS, floats: [h: Lp][t: Lp][scores: 1 + cpc | 2 counters, rel_scrp]
+// [bitmap: rel_bmw words][slots: nslot × Lp], Lp = refine_lp(Le) — a relation
+// row, or RotatE's [cos | sin] row, is Le floats wide.  Rows too wide for h, t
+// and one slot (in_place) are all read where they lie (rel_slots:
+// kge_internal.h).
+
+// element k of the (h, r', t) triple's reduction; row: the relation row, RotatE: [cos | sin]
+template <int M>
+__device__ __forceinline__ float rel_elem(const float* hs, const float* ts, const float* row, int k, int K,
+                                          const Consts& c) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  const float xa = hs[k], xb = CPLX ? hs[K + k] : 0.f;
+  const float ra = (M == ROTATE) ? 0.f : row[k], rb = (M == COMPLEX) ? row[K + k] : 0.f;
+  float qa, qb;
+  ref_make_q<M, TAIL_BATCH>(xa, xb, ra, rb, c, qa, qb, (M == ROTATE) ? row : nullptr, k, K);
+  return ref_elem<M, TAIL_BATCH>(qa, qb, ts[k], CPLX ? ts[K + k] : 0.f, c);
+}
+
+// reference-order score by one half-wave, rows wherever they lie (ref_score_half's reductions)
+template <int M>
+__device__ __forceinline__ float rel_score_half(const float* hs, const float* ts, const float* row, int K,
+                                                const Consts& c, int hl) {
+  auto elem = [&](int k) -> float { return rel_elem<M>(hs, ts, row, k, K, c); };
+  if constexpr (M == TRANSE) {
+    float acc = 0.f;
+    for (int k0 = 0; k0 < K; k0 += 32) {
+      const int k = k0 + hl;
+      const float v = (k < K) ? elem(k) : 0.f;
+      const int m = (K - k0 < 32) ? (K - k0) : 32;
+      for (int j = 0; j < m; ++j) acc += half_shfl(v, j);
+    }
+    return ref_finish<M>(acc, c);
+  } else {
+    // eight rows of 32 elements evaluated before they are added: an element
+    // reads h, r' and t from LDS (RotatE six values), and one row at a time
+    // left every read's latency exposed (FB15k's shape: DistMult d = 2000 29.1 ms
+    // per call, 18.6 ms with eight; RotatE d = 1000 43.4 → 31.3 ms)
+    return ref_finish<M>(ref_cascade_half<float, decltype(elem), 8>(elem, K, hl), c);
+  }
+}
+
+// TransE over a relation row staged in the half's own slot: the elements
+// |(h + r') − t| over the row, then added from 16-byte broadcast reads in
+// ascending k (cand_score_transe_lds), 32 floats read ahead of their adds
+__device__ __forceinline__ float rel_score_transe_lds(const float* hs, const float* ts, float* row, int K,
+                                                      const Consts& c, int hl) {
+  for (int k0 = hl; k0 < K; k0 += 128) {  // four elements' reads before their writes
+    float e[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + 32 * u;
+      e[u] = (k < K) ? rel_elem<TRANSE>(hs, ts, row, k, K, c) : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k0 + 32 * u < K) row[k0 + 32 * u] = e[u];
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  float acc = 0.f;
+  int k = 0;
+  for (; k + 32 <= K; k += 32) {
+    tf4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const tf4*>(row + k + 4 * u);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc += v[u].x;
+      acc += v[u].y;
+      acc += v[u].z;
+      acc += v[u].w;
+    }
+  }
+  for (; k + 4 <= K; k += 4) {
+    const tf4 v = *reinterpret_cast<const tf4*>(row + k);
+    acc += v.x;
+    acc += v.y;
+    acc += v.z;
+    acc += v.w;
+  }
+  for (; k < K; ++k) acc += row[k];
+  return ref_finish<TRANSE>(acc, c);
+}
+
+// PQ, VW: as k_rank_cand
+template <int M, int PQ, int VW>
+__global__ __launch_bounds__(256) void k_rank_rel(RelRankArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float rsm[];
+  constexpr bool IN_PLACE = PQ < 0;
+  using T = typename CandSlot<VW>::T;
+  const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
+  const int64_t qi = (int64_t)blockIdx.x / a.chunks;
+  const int64_t ch = (int64_t)blockIdx.x - qi * a.chunks;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  const int64_t j0 = ch * a.cpc;
+  const int n = (int)((a.R - j0 < a.cpc) ? (a.R - j0) : a.cpc);  // ≥ 1
+  if (!(h >= 0 && h < a.E && t >= 0 && t < a.E && r >= -1 && r < a.R)) {  // (block-uniform)
+    if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+    if (a.scores)
+      for (int j = tid; j < n; j += 256) a.scores[qi * a.R + j0 + j] = NAN;
+    return;  // rank 0, ties 0: k_rank_cand_emit
+  }
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int Le = a.Le, Lp = refine_lp(Le);
+  const int items = n + 1;
+  float* scr = rsm + (IN_PLACE ? 0 : 2 * Lp);
+  int* cnt_s = reinterpret_cast<int*>(scr + a.cpc + 1);
+  uint32_t* bm = reinterpret_cast<uint32_t*>(scr + rel_scrp(a.cpc));
+  float* slots = scr + rel_scrp(a.cpc) + rel_bmw(a.cpc);
+  const float* hs = a.ent + h * Le;
+  const float* ts = a.ent + t * Le;
+  if constexpr (!IN_PLACE) {
+    for (int k = tid; k < Le; k += 256) {
+      rsm[k] = hs[k];
+      rsm[Lp + k] = ts[k];
+    }
+    hs = rsm;
+    ts = rsm + Lp;
+  }
+  if (tid < 2) cnt_s[tid] = 0;
+  for (int w = tid; w < rel_bmw(a.cpc); w += 256) bm[w] = 0u;
+  __syncthreads();
+  if (a.filt_off && r >= 0) {  // the excluded ids of this chunk (any order, repeats, ids outside [0, R): harmless)
+    const int64_t f1 = a.filt_off[qi + 1];
+    for (int64_t i = a.filt_off[qi] + tid; i < f1; i += 256) {
+      const int64_t x = a.filt_ids[i] - j0;
+      if (x >= 0 && x < n) atomicOr(&bm[x >> 5], 1u << (x & 31));
+    }
+  }
+  // relation rows: RotatE walks the trig table's [cos | sin] rows (2·Lr = Le floats)
+  const float* tab = (M == ROTATE) ? a.trig : a.rel;
+  const int64_t r0 = r >= 0 ? r : 0;
+  const int ns = IN_PLACE ? 8 : a.nslot;
+  if (half < ns) {
+    auto item_row = [&](int i) -> const float* {  // the half's i-th item
+      const int j = half + ns * i;
+      return tab + (j == 0 ? r0 : j0 + j - 1) * Le;
+    };
+    auto score_item = [&](int j, float* row) __attribute__((always_inline)) {
+      float sc;
+      if constexpr (M == TRANSE && !IN_PLACE) sc = rel_score_transe_lds(hs, ts, row, a.K, c, hl);
+      else sc = rel_score_half<M>(hs, ts, row, a.K, c, hl);
+      if (hl == 0) scr[j] = sc;
+      // (the score depends on every element of the row: the row's reads are done
+      // before the next item overwrites it)
+      asm volatile("" ::: "memory");
+    };
+    const int nit = (items - half + ns - 1) / ns;  // the half's items (≤ 0: none)
+    if constexpr (IN_PLACE) {
+      for (int i = 0; i < nit; ++i) score_item(half + ns * i, const_cast<float*>(item_row(i)));  // never written
+    } else {
+      float* const row_l = slots + half * Lp;
+      const int nT = Le / VW;
+      T* const rT = reinterpret_cast<T*>(row_l);
+      const T zero = T();
+      if constexpr (PQ > 0) {
+        T nx[PQ > 0 ? PQ : 1];
+        auto fetch = [&](int i) __attribute__((always_inline)) {
+          const T* sT = reinterpret_cast<const T*>(item_row(i));
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            nx[u] = (k < nT) ? sT[k] : zero;
+          }
+        };
+        if (nit > 0) fetch(0);
+        for (int i = 0; i < nit; ++i) {
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            if (k < nT) rT[k] = nx[u];
+          }
+          if (i + 1 < nit) fetch(i + 1);
+          // the half's lanes read each other's writes: one wave's LDS operations complete in order
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l);
+        }
+      } else {
+        for (int i = 0; i < nit; ++i) {
+          const T* sT = reinterpret_cast<const T*>(item_row(i));
+          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
+            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
+            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
+                    v3 = b3 ? sT[k0 + 96] : zero;
+            rT[k0] = v0;
+            if (b1) rT[k0 + 32] = v1;
+            if (b2) rT[k0 + 64] = v2;
+            if (b3) rT[k0 + 96] = v3;
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (a.scores)
+    for (int j = 1 + tid; j <= n; j += 256) a.scores[qi * a.R + j0 + j - 1] = scr[j];
+  if (r < 0) return;  // (block-uniform) prediction: no true relation, nothing to count
+  const float st = scr[0];
+  int g = 0, e_ = 0;
+  for (int j = 1 + tid; j <= n; j += 256) {
+    const int x = j - 1;
+    if (j0 + x == r || ((bm[x >> 5] >> (x & 31)) & 1u)) continue;  // the true relation itself; excluded
+    g += (scr[j] > st);
+    e_ += (scr[j] == st);
+  }
+  g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
+  e_ = (int)wave_sum((float)e_);
+  if ((tid & 63) == 0 && (g | e_)) {
+    atomicAdd(&cnt_s[0], g);
+    atomicAdd(&cnt_s[1], e_);
+  }
+  __syncthreads();
+  if (tid == 0) {  // integer sums: any order of the chunks gives the same counts
+    if (cnt_s[0]) atomicAdd(&a.gt[qi], cnt_s[0]);
+    if (cnt_s[1]) atomicAdd(&a.eq[qi], cnt_s[1]);
+  }
+}
+
+template <int M>
+int launch_rank_rel(const RelRankArgs& a, hipStream_t s) {
+  const int Lp = refine_lp(a.Le);
+  const size_t lds =
+      sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (2 + a.nslot)) + rel_scrp(a.cpc) + rel_bmw(a.cpc));
+  const dim3 grid((unsigned)(a.nq * a.chunks));
+  auto go = [&](auto k) {
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
+    return (int)hipGetLastError();
+  };
+  const int nT = a.vec4 ? a.Le >> 2 : a.Le;  // slots per row
+  if (a.in_place) return go(k_rank_rel<M, -1, 1>);
+  if (a.vec4) {
+    if (nT <= 128) return go(k_rank_rel<M, 4, 4>);
+    if (nT <= 256) return go(k_rank_rel<M, 8, 4>);
+    if (nT <= 512) return go(k_rank_rel<M, 16, 4>);
+    return go(k_rank_rel<M, 0, 4>);
+  }
+  if (nT <= 128) return go(k_rank_rel<M, 4, 1>);
+  if (nT <= 256) return go(k_rank_rel<M, 8, 1>);
+  if (nT <= 512) return go(k_rank_rel<M, 16, 1>);
+  return go(k_rank_rel<M, 0, 1>);
+}
+
 // ------------------------------------------------------------ dispatch
 template <int M, int MODE, int VEC, int NS>
 struct Launch {
@@ -3088,6 +3351,7 @@ struct ModelTable {
     o.topk = &ModelTable<M>::topk;                                                                 \
     o.topk_tile = &launch_topk_tile<M>;                                                            \
     o.rank_cand = &launch_rank_cand<M>;                                                            \
+    o.rank_rel = &launch_rank_rel<M>;                                                              \
     return o;                                                                                      \
   }                                                                                                \
   }

@@ -925,6 +925,25 @@ int launch_rank_emit(const EmitArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// kge_rank_relations, RotatE without a caller's table: the [R, 2, Lr] cos_rn |
+// sin_rn of every relation phase, once per call — not a double-precision cos /
+// sin per (query, relation, element)
+__global__ __launch_bounds__(256) void k_rel_trig_table(const float* __restrict__ rel, int64_t R, int Lr, float kappa,
+                                                        float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= R * Lr) return;
+  const int64_t r = i / Lr;
+  const int k = (int)(i - r * Lr);
+  const float th = rel[i] / kappa;  // model.py:209
+  out[r * 2 * Lr + k] = cos_rn(th);
+  out[r * 2 * Lr + Lr + k] = sin_rn(th);
+}
+
+int launch_rel_trig_table(const float* rel, int64_t R, int Lr, float kappa, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_rel_trig_table, dim3((unsigned)((R * Lr + 255) / 256)), dim3(256), 0, s, rel, R, Lr, kappa, out);
+  return (int)hipGetLastError();
+}
+
 int launch_rank_cand_emit(const int64_t* queries, int64_t nq, int64_t E, int64_t R, const int32_t* gt,
                           const int32_t* eq, int64_t* ranks, int32_t* ties, hipStream_t s) {
   hipLaunchKernelGGL(k_rank_cand_emit, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, queries, nq, E, R, gt, eq,

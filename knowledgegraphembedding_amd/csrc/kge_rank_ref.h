@@ -130,7 +130,11 @@ __device__ __forceinline__ tf2 half_shfl(tf2 v, int src_hl) { return tf2{half_sh
 // the 8 vector lanes added in order.  Lane hl = 8·col + p owns elements
 // 32·row + hl.  T = tf2 runs two sums through the same cascade side by side
 // (the pRotatE screen's lower and upper bounds).
-template <class T, class F>
+// U > 1: the rows' elements are evaluated U at a time before they are added
+// (a remainder one at a time), in the same order
+// to the same accumulator — the same sum, with U rows' loads in flight instead
+// of one row's (k_rank_rel; U = 1 is the loop as the other callers compile it).
+template <class T, class F, int U = 1>
 __device__ T ref_cascade_half(F elem, int K, int hl) {
   const int nvec = K / 8;
   const int size = nvec / 4;
@@ -140,8 +144,20 @@ __device__ T ref_cascade_half(F elem, int K, int hl) {
   const int64_t mask = step - 1;
   T acc[4] = {T{}, T{}, T{}, T{}};
   int i = 0;
+  auto rows = [&](int n) __attribute__((always_inline)) {  // rows i .. i + n − 1 into acc[0], ascending
+    if constexpr (U > 1) {
+      for (; n >= U; n -= U, i += U) {
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = elem(32 * (i + u) + hl);
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[0] += v[u];
+      }
+    }
+    for (; n > 0; --n, ++i) acc[0] += elem(32 * i + hl);
+  };
   while (i + step <= size) {
-    for (int j = 0; j < step; ++j, ++i) acc[0] += elem(32 * i + hl);
+    rows(step);
 #pragma unroll
     for (int lv = 1; lv < 4; ++lv) {
       acc[lv] += acc[lv - 1];
@@ -149,7 +165,7 @@ __device__ T ref_cascade_half(F elem, int K, int hl) {
       if ((i & (mask << (lv * lp))) != 0) break;
     }
   }
-  for (; i < size; ++i) acc[0] += elem(32 * i + hl);
+  rows(size - i);
   T col = acc[0];
 #pragma unroll
   for (int lv = 1; lv < 4; ++lv) col += acc[lv];

@@ -8,6 +8,8 @@
 //   kge::train_step_grads  train_step up to loss.backward()       model.py:252-301
 //   kge::rank_filtered     test_step's filtered ranking           model.py:383-418
 //   kge::rank_candidates   ranks against per-query candidate lists (no reference counterpart: forward + compare)
+//   kge::rank_relations    relation prediction: every relation's 'single' score, the true one ranked (no
+//                          reference counterpart: forward over nq x R triples + compare)
 //   kge::topk              top-k link prediction (no reference counterpart: forward + torch.topk)
 //   kge::sample_negatives  TrainDataset.__getitem__ + collate_fn  dataloader.py:34-66
 //   kge::error_flag        the device error flag the kernels OR into (IndexError on read)
@@ -436,6 +438,68 @@ std::tuple<Tensor, Tensor> rank_candidates_meta(const Tensor& entity, const Tens
           at::empty_symint({queries.sym_size(0)}, o.dtype(at::kInt))};
 }
 
+// ------------------------------------------------------ relation prediction
+// kge_rank_relations: every query scored with every relation; per-query filter
+// lists (filt_off [nq + 1], filt_ids) or none; with_scores: the [nq, R] scores
+// as the third result (else an empty [0, R] tensor)
+std::tuple<Tensor, Tensor, Tensor> rank_relations_cuda(const Tensor& entity, const Tensor& relation,
+                                                       const optional<Tensor>& modulus, const Tensor& queries,
+                                                       const optional<Tensor>& filt_off,
+                                                       const optional<Tensor>& filt_ids, int64_t model, double gamma,
+                                                       double erange, const optional<Tensor>& relation_trig,
+                                                       bool with_scores) {
+  check_model_mode(model, KGE_TAIL_BATCH, true);
+  const c10::Device dev = require_device({&entity, &relation, modulus ? &*modulus : nullptr, &queries});
+  c10::DeviceGuard guard(dev);
+  kge_model_desc d = make_desc(model, entity, relation, gamma, erange, modulus);
+  if (relation_trig.has_value() && relation_trig->defined() && model == KGE_ROTATE) {
+    const Tensor& tr = *relation_trig;
+    TORCH_CHECK(tr.device() == dev && tr.scalar_type() == at::kFloat && tr.is_contiguous() && tr.dim() == 3 &&
+                    tr.size(0) == d.nrelation && tr.size(1) == 2 && tr.size(2) == d.relation_dim,
+                "relation_trig: expected a contiguous float32 [", d.nrelation, ", 2, ", d.relation_dim,
+                "] tensor on ", dev);
+    d.relation_trig = tr.data_ptr<float>();
+  }
+  const Tensor q = as_index(queries, dev);
+  TORCH_CHECK(q.dim() == 2 && q.size(1) == 3, "queries must be [nq, 3], got ", q.sizes());
+  const int64_t nq = q.size(0);
+  const bool filtered = filt_off.has_value() && filt_off->defined();
+  TORCH_CHECK_VALUE(filtered == (filt_ids.has_value() && filt_ids->defined()),
+                    "filt_off and filt_ids: both or neither");
+  Tensor off, ids;
+  if (filtered) {
+    TORCH_CHECK_VALUE(filt_off->dim() == 1 && filt_off->numel() == nq + 1, "filt_off must be [nq + 1] = [", nq + 1,
+                      "], got ", filt_off->sizes());
+    off = as_index(*filt_off, dev);
+    ids = filt_ids->numel() ? as_index(*filt_ids, dev) : at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(dev));
+  }
+  Tensor ranks = at::empty({nq}, at::TensorOptions().dtype(at::kLong).device(dev));
+  Tensor ties = at::empty({nq}, at::TensorOptions().dtype(at::kInt).device(dev));
+  Tensor scores = at::empty({with_scores ? nq : 0, d.nrelation}, at::TensorOptions().dtype(at::kFloat).device(dev));
+  if (nq == 0) return {ranks, ties, scores};
+  Tensor ws = workspace(kge_rank_relations_workspace_bytes(&d, nq), dev);
+  check_status(kge_rank_relations(&d, q.data_ptr<int64_t>(), nq, filtered ? off.data_ptr<int64_t>() : nullptr,
+                                  filtered ? ids.data_ptr<int64_t>() : nullptr, ranks.data_ptr<int64_t>(),
+                                  ties.data_ptr<int32_t>(), with_scores ? scores.data_ptr<float>() : nullptr,
+                                  ws.data_ptr(), (size_t)ws.numel(), error_flag_for(dev).data_ptr<int32_t>(),
+                                  current_stream(dev)),
+               "kge_rank_relations");
+  return {ranks, ties, scores};
+}
+
+std::tuple<Tensor, Tensor, Tensor> rank_relations_meta(const Tensor& entity, const Tensor& relation,
+                                                       const optional<Tensor>& modulus, const Tensor& queries,
+                                                       const optional<Tensor>& filt_off,
+                                                       const optional<Tensor>& filt_ids, int64_t model, double gamma,
+                                                       double erange, const optional<Tensor>& relation_trig,
+                                                       bool with_scores) {
+  check_model_mode(model, KGE_TAIL_BATCH, true);
+  auto o = queries.options();
+  const c10::SymInt nq = queries.sym_size(0);
+  return {at::empty_symint({nq}, o.dtype(at::kLong)), at::empty_symint({nq}, o.dtype(at::kInt)),
+          at::empty_symint({with_scores ? nq : c10::SymInt(0), relation.sym_size(0)}, o.dtype(at::kFloat))};
+}
+
 // -------------------------------------------------------------------- top-k
 // kge_topk with per-query filter lists (filt_off [nq + 1], filt_ids) or none;
 // more than 65535 queries go in several calls
@@ -565,6 +629,12 @@ std::tuple<Tensor, Tensor> rank_candidates_cpu(const Tensor&, const Tensor&, con
   check_model_mode(model, mode, true);
   return refuse_cpu<std::tuple<Tensor, Tensor>>();
 }
+std::tuple<Tensor, Tensor, Tensor> rank_relations_cpu(const Tensor&, const Tensor&, const optional<Tensor>&,
+                                                      const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
+                                                      int64_t model, double, double, const optional<Tensor>&, bool) {
+  check_model_mode(model, KGE_TAIL_BATCH, true);
+  return refuse_cpu<std::tuple<Tensor, Tensor, Tensor>>();
+}
 std::tuple<Tensor, Tensor> topk_cpu(const Tensor&, const Tensor&, const optional<Tensor>&, const Tensor&,
                                     const optional<Tensor>&, const optional<Tensor>&, int64_t mode, int64_t model,
                                     double, double, int64_t, int64_t) {
@@ -592,6 +662,9 @@ TORCH_LIBRARY(kge, m) {
         "Tensor? relation_trig=None) -> (Tensor, Tensor)");
   m.def("rank_candidates(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor cand, int mode, "
         "int model, float gamma, float embedding_range, Tensor? relation_trig=None) -> (Tensor, Tensor)");
+  m.def("rank_relations(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor? filt_off, "
+        "Tensor? filt_ids, int model, float gamma, float embedding_range, Tensor? relation_trig=None, "
+        "bool with_scores=False) -> (Tensor, Tensor, Tensor)");
   m.def("topk(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries, Tensor? filt_off, Tensor? filt_ids, "
         "int mode, int model, float gamma, float embedding_range, int k, int path=0) -> (Tensor, Tensor)");
   m.def("sample_negatives(Tensor triples, Tensor batch, int nentity, int negative_sample_size, Tensor true_off, "
@@ -607,6 +680,7 @@ TORCH_LIBRARY_IMPL(kge, CUDA, m) {
   m.impl("train_step_grads", &train_step_grads_cuda);
   m.impl("rank_filtered", &rank_filtered_cuda);
   m.impl("rank_candidates", &rank_candidates_cuda);
+  m.impl("rank_relations", &rank_relations_cuda);
   m.impl("topk", &topk_cuda);
   m.impl("sample_negatives", &sample_negatives_cuda);
 }
@@ -617,6 +691,7 @@ TORCH_LIBRARY_IMPL(kge, Meta, m) {
   m.impl("train_step_grads", &train_step_grads_meta);
   m.impl("rank_filtered", &rank_filtered_meta);
   m.impl("rank_candidates", &rank_candidates_meta);
+  m.impl("rank_relations", &rank_relations_meta);
   m.impl("topk", &topk_meta);
   m.impl("sample_negatives", &sample_negatives_meta);
 }
@@ -627,6 +702,7 @@ TORCH_LIBRARY_IMPL(kge, CPU, m) {
   m.impl("train_step_grads", &train_step_grads_cpu);
   m.impl("rank_filtered", &rank_filtered_cpu);
   m.impl("rank_candidates", &rank_candidates_cpu);
+  m.impl("rank_relations", &rank_relations_cpu);
   m.impl("topk", &topk_cpu);
   m.impl("sample_negatives", &sample_negatives_cpu);
 }

@@ -175,6 +175,40 @@ class FilterIndex:
         np.cumsum(per, out=off[1:])
         return off, ids.astype(np.int64)
 
+    def _relation_index(self):
+        """(sorted keys h·E + t, relation ids) of the true triples, made from the
+        host arrays on first use (relation prediction only)."""
+        idx = self.__dict__.get('_rel_index')
+        if idx is None:
+            R, E = self.nrelation, self.nentity
+            h, r = self._k_hr // R, self._k_hr % R
+            key = h * E + self._tails
+            o = np.lexsort((r, key))
+            idx = self.__dict__['_rel_index'] = (key[o], r[o].astype(np.int64))
+        return idx
+
+    def relation_csr(self, queries):
+        """(offsets [nq+1] int64, ids int64): per query (h, r, t) the relations
+        r' != r with (h, r', t) a true triple, ascending — the filter lists of
+        relation prediction (kge_rank_relations).  r = -1 (no true relation)
+        keeps every known relation of (h, t)."""
+        q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+        cand, vals = self._relation_index()
+        keys = q[:, 0] * self.nentity + q[:, 2]
+        lo, hi = np.searchsorted(cand, keys, side='left'), np.searchsorted(cand, keys, side='right')
+        cnt = hi - lo
+        total = int(cnt.sum())
+        if total == 0:
+            return np.zeros(len(q) + 1, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        starts = np.repeat(lo - np.concatenate(([0], np.cumsum(cnt)[:-1])), cnt)
+        ids = vals[starts + np.arange(total)]
+        owner = np.repeat(np.arange(len(q)), cnt)
+        keep = ids != q[owner, 1]
+        ids, owner = ids[keep], owner[keep]
+        off = np.zeros(len(q) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(owner, minlength=len(q)), out=off[1:])
+        return off, ids.astype(np.int64)
+
     def filtered(self, triple, mode: str) -> np.ndarray:
         off, ids = self.filter_csr([triple], mode)
         return ids[off[0]:off[1]]

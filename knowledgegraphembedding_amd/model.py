@@ -579,7 +579,7 @@ class KGEModel(nn.Module):
                 for ranks in out:  # head-batch blocks, then tail-batch
                     ranks_seq.extend(ranks.cpu().numpy().tolist())
                 ops.raise_on_device_error(dev)
-            return _rank_metrics(ranks_seq)
+            return model._relation_metrics(_rank_metrics(ranks_seq), test_triples, all_true_triples)
 
         # Filtered MRR / MR / HITS@{1,3,10}: head-batch queries, then tail-batch
         # (model.py:349-418); the filter is dataloader.py:134-154's.
@@ -646,7 +646,8 @@ class KGEModel(nn.Module):
                 ranks_np = torch.cat(ranks_all).cpu().numpy() if ranks_all else np.zeros(0, np.int64)
                 ranks_seq.extend(ranks_np.tolist())
             ops.raise_on_device_error(dev)
-        return _rank_metrics(ranks_seq)
+        # (KGE_EVAL_RELATIONS=1: plus the filtered relation ranks, REL_*)
+        return model._relation_metrics(_rank_metrics(ranks_seq), triples, index)
 
     # sampled evaluation (KGE_EVAL_CANDIDATES): queries per sampler / ranking launch
     EVAL_SAMPLE_BLOCK = 16384
@@ -719,6 +720,102 @@ class KGEModel(nn.Module):
         with torch.no_grad():
             ranks, ties = self._rank_candidates_device(q, cand, mode, self._rank_rotation(dev, relation_trig))
         res = ranks.cpu().numpy(), ties.cpu().numpy()
+        ops.raise_on_device_error(dev)
+        return res
+
+    # ------------------------------------------------- relation prediction
+    def _relation_index(self, all_true_triples, dev):
+        if all_true_triples is None or isinstance(all_true_triples, FilterIndex):
+            return all_true_triples
+        return FilterIndex(all_true_triples, self.nentity, self.nrelation, device=dev)
+
+    def _relation_metrics(self, metrics, test_triples, all_true_triples):
+        """test_step with KGE_EVAL_RELATIONS=1: the filtered relation ranks of
+        the same triples, as REL_MRR / REL_MR / REL_HITS@{1,3,10}; unset (or
+        0), `metrics` as it is."""
+        if (os.environ.get("KGE_EVAL_RELATIONS", "0") or "0") == "0":
+            return metrics
+        ranks, _ = self.rank_relations(test_triples, all_true_triples)
+        metrics.update({'REL_' + k: v for k, v in _rank_metrics(ranks.tolist()).items()})
+        return metrics
+
+    def rank_relations(self, triples, all_true_triples=None, relation_trig=None):
+        """Relation prediction ranks: per (h, r, t) row of `triples` the rank of
+        r among all relations r' scored as (h, r', t) and the tie count (numpy
+        int64, int32), in the reference's fp32 'single'-mode score order
+        (ops.rank_relations): rank = 1 + the other relations scoring above r,
+        ties = those scoring equal.  With `all_true_triples` (a triple list or
+        a FilterIndex) the other known relations of (h, t) are excluded
+        (filtered ranks); without, raw ranks.  RotatE's rotation table defaults
+        per `rank_trig` (see _rank_rotation); pRotatE uses the correctly rounded
+        device sin."""
+        dev = ops._require_device(self.entity_embedding)
+        index = self._relation_index(all_true_triples, dev)
+        q = triples_array(triples)
+        desc = self.desc()
+        # queries per launch, as test_step (results do not depend on it)
+        block = min(16384, max(256, (128 << 20) // (4 * int(self.entity_dim))))
+        out = []
+        with torch.no_grad():
+            trig = self._rank_rotation(dev, relation_trig)
+            for b0 in range(0, len(q), block):
+                qb = np.array(q[b0:b0 + block], dtype=np.int64, order='C')  # (a copy: the input may be read-only)
+                filt = None
+                if index is not None:
+                    filt = tuple(torch.from_numpy(x) for x in index.relation_csr(qb))
+                out.append(ops.rank_relations(desc, torch.from_numpy(qb), dev, filt=filt, relation_trig=trig))
+        ranks = torch.cat([o[0] for o in out]).cpu().numpy() if out else np.zeros(0, np.int64)
+        ties = torch.cat([o[1] for o in out]).cpu().numpy() if out else np.zeros(0, np.int32)
+        ops.raise_on_device_error(dev)
+        return ranks, ties
+
+    # predict_relations: bytes of the [chunk, nrelation] fp32 score buffer per launch
+    REL_SCORE_BYTES = 128 << 20
+
+    def predict_relations(self, pairs, k=10, all_true_triples=None):
+        """Top-k relation prediction: for every (h, t) row of `pairs` ([nq, 2],
+        or [nq, 3] rows (h, r, t) whose r is not read) the k best relations as
+        numpy (ids [nq, k] int64, scores [nq, k] float32), best first — equal
+        scores in ascending id — in the reference's fp32 'single'-mode scores
+        (ops.rank_relations with r = -1).  `all_true_triples` (a triple list or
+        a FilterIndex): the known relations of (h, t) are excluded.  NaN scores
+        are never selected; the output is padded with (-1, -inf) when fewer than
+        k relations remain."""
+        R = int(self.nrelation)
+        if not 1 <= int(k) <= R:
+            raise ValueError('k = %s: expected 1 .. %d (nrelation)' % (k, R))
+        k = int(k)
+        dev = ops._require_device(self.entity_embedding)
+        index = self._relation_index(all_true_triples, dev)
+        p = np.asarray(pairs, dtype=np.int64)
+        p = p.reshape(-1, 3)[:, (0, 2)] if (p.ndim == 2 and p.shape[1] == 3) else p.reshape(-1, 2)
+        q = np.full((len(p), 3), -1, dtype=np.int64)  # r = -1: no true relation
+        q[:, 0], q[:, 2] = p[:, 0], p[:, 1]
+        desc = self.desc()
+        chunk = max(1, self.REL_SCORE_BYTES // (4 * R))
+        ids_out, sc_out = [], []
+        with torch.no_grad():
+            trig = self._rank_rotation(dev)
+            for b0 in range(0, len(q), chunk):
+                qb = np.ascontiguousarray(q[b0:b0 + chunk])
+                _, _, s = ops.rank_relations(desc, torch.from_numpy(qb), dev, relation_trig=trig, scores=True)
+                valid = ~torch.isnan(s)
+                if index is not None:
+                    off, ids = index.relation_csr(qb)
+                    if len(ids):
+                        owner = np.repeat(np.arange(len(qb)), np.diff(off))
+                        valid[torch.from_numpy(owner).to(dev), torch.from_numpy(ids).to(dev)] = False
+                # (score descending, id ascending) among the valid ones: a stable
+                # sort by score, then a stable sort that moves the invalid ones last
+                key = torch.where(valid, s, torch.full_like(s, float('-inf')))
+                o1 = torch.sort(key, dim=1, descending=True, stable=True).indices
+                o2 = torch.sort((~torch.gather(valid, 1, o1)).to(torch.int8), dim=1, stable=True).indices
+                order = torch.gather(o1, 1, o2)[:, :k]
+                ok = torch.gather(valid, 1, order)
+                ids_out.append(torch.where(ok, order, torch.full_like(order, -1)))
+                sc_out.append(torch.where(ok, torch.gather(s, 1, order), torch.full_like(s[:, :k], float('-inf'))))
+        res = (torch.cat(ids_out).cpu().numpy() if ids_out else np.zeros((0, k), np.int64),
+               torch.cat(sc_out).cpu().numpy() if sc_out else np.zeros((0, k), np.float32))
         ops.raise_on_device_error(dev)
         return res
 

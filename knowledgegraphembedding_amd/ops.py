@@ -596,6 +596,49 @@ def rank_candidates(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, cand
     return ranks, ties
 
 
+def rank_relations(desc: _lib.ModelDesc, queries: torch.Tensor, dev, filt=None,
+                   relation_trig: Optional[torch.Tensor] = None, scores: bool = False):
+    """Relation prediction (kge_rank_relations): every query (h, r, t) scored
+    with every relation r' in the reference's fp32 'single'-mode order.
+    Returns device tensors (ranks int64, ties int32[, scores [nq, R] float32]):
+    rank = 1 + the relations other than r, and not excluded, scoring above r,
+    ties = those scoring equal.  `filt` = (filt_off [nq + 1], filt_ids): per-query
+    lists of relation ids to exclude (FilterIndex.relation_csr); None: raw ranks.
+    r = -1 means "no true relation": rank 0, ties 0, the scores are written.
+    `relation_trig` as for rank_filtered (RotatE without one: correctly rounded
+    on the device).  The device error flag is left for the caller's next read
+    (raise_on_device_error): a query with h, t or r out of range has rank 0,
+    ties 0 and a NaN score row."""
+    if relation_trig is not None:
+        shape = (desc.nrelation, 2, desc.relation_dim)
+        if (tuple(relation_trig.shape) != shape or relation_trig.dtype != torch.float32
+                or not relation_trig.is_contiguous() or relation_trig.device != dev):
+            raise ValueError(f"relation_trig: expected a contiguous float32 {shape} tensor on {dev}")
+        desc = _lib.ModelDesc.from_buffer_copy(desc)
+        desc.relation_trig = relation_trig.data_ptr()
+    q = _idx(queries, dev)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"queries: {tuple(q.shape)}, expected [nq, 3]")
+    nq = q.shape[0]
+    off = ids = None
+    if filt is not None:
+        _check_filter_shape(desc, nq, filt[0], False)
+        off = _idx(filt[0], dev)
+        ids = _idx(filt[1], dev) if filt[1].numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+    ranks = torch.empty(nq, dtype=torch.int64, device=dev)
+    ties = torch.empty(nq, dtype=torch.int32, device=dev)
+    out_s = torch.empty(nq, desc.nrelation, dtype=torch.float32, device=dev) if scores else None
+    lib = _lib.load()
+    st = state(dev)
+    ws = st.workspace(lib.kge_rank_relations_workspace_bytes(desc, nq))  # (clears rank_ws_ptr: the table buffers go)
+    _lib.check(
+        lib.kge_rank_relations(desc, q.data_ptr(), nq, _ptr(off), _ptr(ids), ranks.data_ptr(), ties.data_ptr(),
+                               _ptr(out_s), ws.data_ptr(), ws.numel(), st.err.data_ptr(), _stream(dev)),
+        "kge_rank_relations",
+    )
+    return (ranks, ties, out_s) if scores else (ranks, ties)
+
+
 TOPK_MAX_K = 128  # kge_hip.h KGE_TOPK_MAX_K
 TOPK_PATHS = {"auto": 0, "tile": 2, "scan": 3}
 

@@ -20,6 +20,10 @@ same library with no Python in the call path:
     kge::rank_candidates(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries,
                          Tensor cand, int mode, int model, float gamma, float embedding_range,
                          Tensor? relation_trig=None) -> (Tensor, Tensor)
+    kge::rank_relations(Tensor entity, Tensor relation, Tensor? modulus, Tensor queries,
+                        Tensor? filt_off, Tensor? filt_ids, int model, float gamma,
+                        float embedding_range, Tensor? relation_trig=None,
+                        bool with_scores=False) -> (Tensor, Tensor, Tensor)
     kge::sample_negatives(..., Tensor(a!) pos_out, Tensor(b!) neg_out, Tensor(c!) w_out) -> ()
     kge::error_flag(Device device) -> Tensor
 
