@@ -15,7 +15,15 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).
  *     Nothing here allocates, frees or synchronises: every call is
  *     graph-capturable.  Scratch comes from a caller-owned workspace whose
- *     size the matching *_workspace_bytes() query returns.
+ *     size the matching *_workspace_bytes() query returns.  The workspace
+ *     must be 256-byte aligned (what hipMalloc gives): its sub-buffers sit at
+ *     256-byte offsets from its base and are read 16 bytes at a time.  A
+ *     call is meant to touch no byte beyond that size and to initialise
+ *     whatever it reads, so the workspace needs no clearing
+ *     (tests/test_arena_gpu.py runs the entries other than kge_ship_step on
+ *     a poisoned workspace of exactly the queried size; the end of the
+ *     training layout is not written at its shapes, so there the exact size
+ *     is exercised but a short one would not be noticed).
  *   - Return value: 0 on success, a KGE_ERR_* code for argument errors
  *     (checked on the host before anything is launched), or a hipError_t
  *     (offset by KGE_ERR_HIP_BASE) if a launch fails.
@@ -178,7 +186,11 @@ int kge_train_step_grads(const kge_model_desc *m, int32_t mode, const int64_t *p
  * [entity_begin, entity_end) only (call it once per chunk, in any order, until
  * every row is covered); FINALIZE joins the relation pass and writes the
  * losses (and the pRotatE modulus gradient).  Same stream, same workspace,
- * same arguments in every phase; ALL = one kge_train_step_grads call. */
+ * same arguments in every phase; ALL = one kge_train_step_grads call.
+ * [entity_begin, entity_end) is read by ENTITY (the rows of its chunk) and
+ * by FINALIZE, which sums the regulariser's entity terms over it: pass
+ * [0, nentity) to FINALIZE (a narrower range leaves the other rows out of
+ * losses_out[2] and [3]).  ROWS ignores the range; any valid one will do. */
 #define KGE_PHASE_ROWS 1
 #define KGE_PHASE_ENTITY 2
 #define KGE_PHASE_FINALIZE 4

@@ -68,6 +68,8 @@ class _DeviceState:
         key = s.cuda_stream
         ws = self.ws.get(key)
         if ws is None or ws.numel() < nbytes:
+            # the 25 % is growth headroom, not a need of the library:
+            # tests/test_arena_gpu.py holds it to the exact size
             ws = self.ws[key] = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=self.dev)
         return ws
 
