@@ -20,7 +20,8 @@
  *     256-byte offsets from its base and are read 16 bytes at a time.  A
  *     call is meant to touch no byte beyond that size and to initialise
  *     whatever it reads, so the workspace needs no clearing
- *     (tests/test_arena_gpu.py runs the entries other than kge_ship_step on
+ *     (tests/test_arena_gpu.py, and tests/test_ship_stages_gpu.py for
+ *     kge_ship_step, run the entries on
  *     a poisoned workspace of exactly the queried size; the end of the
  *     training layout is not written at its shapes, so there the exact size
  *     is exercised but a short one would not be noticed).
@@ -411,6 +412,26 @@ int kge_train_step_from_rows_phased(const kge_model_desc *m, int32_t mode, const
  *                   relations on rank 0 only), pRotatE modulus grad + Adam
  * Same maths as one process on the global batch; the cross-shard sums run in
  * another order, so results agree to fp32 rounding, not bit for bit.
+ *
+ * Workspace: kge_train_workspace_bytes(m, ship->batch, ship->nneg) — the GLOBAL
+ * batch, the same size on every rank; no rank offset enters it.  Same workspace
+ * in every stage of a step (ROWS builds the occurrence CSR that CHAIN and
+ * ENTITY read).  The per-row buffers of kge_ship_desc are the caller's, because
+ * they cross the ranks between the stages; with B = batch, n = nneg, Le =
+ * entity_dim, Lr = relation_dim, in floats, exactly:
+ *   q, qp [B, Le]; part [B, 4]; parts [world, B, 4]; scores, g [B, n];
+ *   dq, pq [B, Le]; pstats [B, 4]; ent_contrib [2B, Le]; rel_contrib [B, Lr];
+ *   row_stats [B, 4].
+ * qp and pq are touched head-batch only (they may be NULL tail-batch).  The
+ * buffers that cross the ranks (q, qp, part, dq, pq, pstats) are written for
+ * every row of the batch, owned or not (zeros where this shard has no share),
+ * so the sums need no clearing; g and scores are written only where this
+ * shard owns the negative, ent_contrib only in rows it owns.  With regularization,
+ * losses_out[3] and the regulariser's part of losses_out[2] are this rank's
+ * share: the caller sums losses_out[3] over the ranks.
+ * (tests/test_ship_stages_gpu.py runs the stages on buffers of exactly these
+ * sizes, every rank's table, gradient and moments inside a full-size poisoned
+ * allocation: no row outside [own_begin, own_end) is read or written.)
  */
 #define KGE_SHIP_Q 1
 #define KGE_SHIP_ROWS 2

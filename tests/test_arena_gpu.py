@@ -27,9 +27,10 @@ After each call and a stream sync:
      rtol = 1e-6 where the regulariser's partial sums may regroup (DistMult /
      ComplEx, as test_entity_pass_column_slices_bitwise), exact elsewhere.
 
-Shapes: tests/arena_cases.py.  kge_ship_step is out of scope: its five stages
-need the collectives between them, test_ship_gpu.py drives it through
-partition.py.  rank_candidates_cases and rank_relations_cases fix R = 7 / their
+Shapes: tests/arena_cases.py.  kge_ship_step has a module of its own: its five
+stages need the collectives between them, which tests/test_ship_stages_gpu.py
+emulates in one process on the same arenas (test_ship_gpu.py drives the real
+ones through partition.py).  rank_candidates_cases and rank_relations_cases fix R = 7 / their
 own R; topk's tables are built here at R = 5 and scored by
 topk_cases.oracle_scores.
 
@@ -71,7 +72,7 @@ after the buffer"), before any value is compared:
                 floats for up to 8 column slices of 128 slots; RotatE at span
                 280 fills 2 slices of 35) and rocPRIM's scan scratch, neither
                 written to its end at these shapes.  kge_ship_step reuses this
-                layout and is out of scope here
+                layout (tests/test_ship_stages_gpu.py runs it at the exact size)
 One build in which the lazy entity pass ignores nrows and walks all places was
 run once, guarded half only: it ended in a GPU memory fault on its first case
 (TransE E = 257, (B, n) = (5, 65)) instead of a failed unchanged() — a place
