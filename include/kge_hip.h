@@ -95,7 +95,8 @@ enum kge_status {
  * relation_embedding are both 16-byte aligned, the kernels read rows in 16-byte slots; any
  * other table runs the same kernels with single-float slots.  With 16-byte slots the
  * gradient passes also write grad_entity / grad_relation, and stream a fused optimizer's
- * param / exp_avg / exp_avg_sq of the entity and relation tables (kge_adam_desc), 16 bytes
+ * param / exp_avg / exp_avg_sq of the entity and relation tables (kge_adam_desc; likewise
+ * kge_adagrad_desc's param / state_sum, but for a row-wise [nentity] state), 16 bytes
  * at a time: kge_score_backward, kge_train_step* and kge_ship_step return KGE_ERR_ARG,
  * before any launch, if one of those buffers is not 16-byte aligned (as kge_adam_step does
  * for its four arrays); relation_trig must then be 16-byte aligned too (kge_rank_filtered*).
@@ -282,6 +283,77 @@ int kge_train_step_lazy(const kge_model_desc *m, int32_t mode, const int64_t *po
                         float regularization, const kge_adam_desc *adam, float *grad_entity, float *grad_relation,
                         float *grad_modulus, float *losses_out, void *workspace, size_t workspace_bytes,
                         int32_t *err_flag, void *stream);
+
+/*
+ * Fused lazy ADAGRAD: kge_train_step_lazy with Adagrad in the place of Adam.
+ * The rule, per element in IEEE fp32, one rounding per operation, no
+ * contraction (lr and eps are the caller's doubles rounded to fp32):
+ *   element-wise (entity_rowwise = 0; always the relation table and the
+ *   pRotatE modulus), state_sum shaped like the parameter:
+ *       s'  = s + g*g
+ *       std = sqrtf(s') + eps
+ *       p'  = p + (-lr) * (g / std)
+ *   row-wise (entity_rowwise = 1, entity table only), state_sum [nentity]:
+ *       G'   = G + (sum_k g_k*g_k) / (float)entity_dim
+ *       std  = sqrtf(G') + eps
+ *       p_k' = p_k + (-lr) * (g_k / std)
+ *     the row sum in a fixed order: each of the 64 lanes adds the squares of
+ *     its own elements in ascending slot order (a complex row's re element
+ *     before the im element of the same dimension), then the wave's fixed tree
+ *     (the order of the regulariser's per-row partial sum).
+ * This is torch.optim.Adagrad's formula with lr_decay = 0, weight_decay = 0 and
+ * initial_accumulator_value = 0 (no other setting is served); its CPU kernel
+ * rounds g*g + s once, so its state can differ from this rule's by an ulp.
+ * eps must be > 0: with eps = 0 an untouched all-zero row would be NaN under
+ * the dense rule and untouched under this one.
+ * A zero gradient changes nothing under the rule (s + 0, p + (-lr)*(0/std)),
+ * so updating only the touched rows IS the dense update:
+ *   A touched row gets the rule from the same gradient bits as kge_train_step
+ *     (same occurrence order, same arithmetic).
+ *   An untouched row's param and state are neither read nor written.
+ *   The result equals applying the rule to every row of the dense gradient,
+ *     bit for bit, at every step (no staleness, unlike the lazy Adam).
+ * Everything else is kge_train_step_lazy's: a whole single-process step;
+ * grad_entity neither read nor written (may be NULL); the touched-row list built
+ * behind the occurrence CSR; no allocation, no synchronisation, capturable.
+ * The row-wise kind runs the row-per-wave entity pass whatever the row length
+ * (the sliced pass never holds a whole row).
+ * Host checks, in this order: opt == NULL (KGE_ERR_ARG); the model; the mode;
+ * grad_relation / losses_out; pos / neg / err_flag / batch / nneg; the
+ * descriptor — struct_size (KGE_ERR_ABI), then, each KGE_ERR_ARG: an entity or
+ * relation param / state_sum missing, a param that is not the model's own table
+ * (pRotatE: a modulus.param that is not the model's or has no state_sum;
+ * modulus.param NULL leaves the modulus alone), eps not > 0 (NaN included), lr
+ * negative or not finite, entity_rowwise outside {0, 1}; regularization != 0
+ * (KGE_ERR_ARG); rows over 2048 floats per (half-)row (KGE_ERR_DIM); with
+ * 16-byte slots, 16-byte alignment of grad_relation and of the streamed param /
+ * state_sum arrays (the row-wise [nentity] state needs float alignment only);
+ * subsampling_weight; pRotatE's grad_modulus; the workspace
+ * (KGE_ERR_WORKSPACE); nneg > 8192 (KGE_ERR_DIM).
+ * Workspace: kge_train_adagrad_workspace_bytes = kge_train_lazy_workspace_bytes.
+ */
+typedef struct kge_adagrad_tensor {
+    float *param;
+    float *state_sum;
+} kge_adagrad_tensor;
+
+typedef struct kge_adagrad_desc {
+    kge_adagrad_tensor entity;
+    kge_adagrad_tensor relation;
+    kge_adagrad_tensor modulus; /* pRotatE only (param NULL otherwise) */
+    float lr, eps;
+    int32_t entity_rowwise;     /* 0: entity.state_sum [nentity, entity_dim]; 1: [nentity] */
+    int32_t write_grad;         /* grad_relation / grad_modulus, as kge_adam_desc.write_grad */
+    int32_t struct_size;        /* = sizeof(kge_adagrad_desc) as the caller compiled it (else KGE_ERR_ABI) */
+} kge_adagrad_desc;
+
+size_t kge_train_adagrad_workspace_bytes(const kge_model_desc *m, int64_t batch, int64_t nneg);
+int kge_train_step_adagrad(const kge_model_desc *m, int32_t mode, const int64_t *pos, const int64_t *neg,
+                           int64_t batch, int64_t nneg, const float *subsampling_weight, const float *weight_sum,
+                           int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
+                           float adversarial_temperature, float regularization, const kge_adagrad_desc *opt,
+                           float *grad_entity, float *grad_relation, float *grad_modulus, float *losses_out,
+                           void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /*
  * Data-parallel FACTOR EXCHANGE (distributed.py, exchange "factors"): instead
@@ -476,6 +548,16 @@ int kge_weight_sum(const float *w, int64_t n, float *out, void *stream);
 int kge_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t numel,
                   float beta1, float beta2, float eps, float step_size, float bias_correction2_sqrt,
                   void *stream);
+
+/*
+ * One dense element-wise Adagrad update (the rule of kge_train_step_adagrad)
+ * over numel elements, like kge_adam_step: every array 16-byte aligned.
+ * KGE_ERR_ARG, in this order: a NULL array or numel < 0; eps not > 0 (NaN
+ * included), lr negative or not finite; (numel == 0 returns KGE_OK here;) an
+ * array that is not 16-byte aligned.
+ */
+int kge_adagrad_step(float *param, const float *grad, float *state_sum, int64_t numel, float lr, float eps,
+                     void *stream);
 
 /*
  * Filtered link-prediction ranks — replaces the per-batch body of

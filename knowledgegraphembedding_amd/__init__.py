@@ -6,6 +6,7 @@ gfx950 (libkge_hip.so, C-ABI in include/kge_hip.h).
 """
 from .dataloader import BidirectionalOneShotIterator, TestDataset, TrainDataset  # noqa: F401
 from .model import KGEModel  # noqa: F401
-from .optim import KGEAdam, KGELazyAdam  # noqa: F401
+from .optim import KGEAdagrad, KGEAdam, KGELazyAdam  # noqa: F401
 
-__all__ = ["KGEModel", "TrainDataset", "TestDataset", "BidirectionalOneShotIterator", "KGEAdam", "KGELazyAdam"]
+__all__ = ["KGEModel", "TrainDataset", "TestDataset", "BidirectionalOneShotIterator", "KGEAdam", "KGELazyAdam",
+           "KGEAdagrad"]

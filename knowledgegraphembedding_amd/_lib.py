@@ -66,6 +66,24 @@ class AdamDesc(C.Structure):
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("write_grad", C.c_int32)]
 
 
+class AdagradTensor(C.Structure):
+    """struct kge_adagrad_tensor."""
+
+    _fields_ = [("param", C.c_void_p), ("state_sum", C.c_void_p)]
+
+
+class AdagradDesc(C.Structure):
+    """struct kge_adagrad_desc (struct_size is set on construction)."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(AdagradDesc)
+
+    _fields_ = [("entity", AdagradTensor), ("relation", AdagradTensor), ("modulus", AdagradTensor),
+                ("lr", C.c_float), ("eps", C.c_float), ("entity_rowwise", C.c_int32), ("write_grad", C.c_int32),
+                ("struct_size", C.c_int32)]
+
+
 class ShipDesc(C.Structure):
     """struct kge_ship_desc (query shipping, kge_ship_step)."""
 
@@ -115,6 +133,12 @@ SIGNATURES = {
         [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _F, C.POINTER(AdamDesc), _P, _P, _P, _P, _P,
          _SZ, _P, _P],
     ),
+    "kge_train_adagrad_workspace_bytes": (_SZ, [_DESC, _I64, _I64]),
+    "kge_train_step_adagrad": (
+        C.c_int,
+        [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _F, C.POINTER(AdagradDesc), _P, _P, _P, _P,
+         _P, _SZ, _P, _P],
+    ),
     "kge_train_rows_slice": (
         C.c_int,
         [_DESC, _I32, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _I32, _F, _P, _P, _P, _P, _SZ, _P, _P],
@@ -145,6 +169,7 @@ SIGNATURES = {
                                 _SZ, _P, _P]),
     "kge_weight_sum": (C.c_int, [_P, _I64, _P, _P]),
     "kge_adam_step": (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
+    "kge_adagrad_step": (C.c_int, [_P, _P, _P, _I64, _F, _F, _P]),
     "kge_rank_workspace_bytes": (_SZ, [_DESC, _I64]),
     "kge_rank_filtered": (C.c_int, [_DESC, _I32, _P, _I64, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_filtered_ex": (C.c_int, [_DESC, _I32, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P, _P]),

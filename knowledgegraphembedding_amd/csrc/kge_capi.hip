@@ -5,6 +5,7 @@
 // Layout: shared helpers, then training (StepCall → StepPlan → the rows /
 // entity / finalize phases), then ranking (RankCall → RankRun → table, queries,
 // tail), then the one extern "C" block whose entries fill a call struct by name.
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -335,6 +336,11 @@ struct StepCall {
     float regularization = 0.f;
   } loss;
   const kge_adam_desc* adam = nullptr;  // the fused optimizer step, or none
+  // kge_train_step_adagrad: the caller's descriptor; train_impl checks it where
+  // it checks Adam's and then carries it in `adam`'s fields (adagrad_view) with
+  // `opt` naming the rule
+  const kge_adagrad_desc* adagrad = nullptr;
+  int opt = OPT_ADAM;  // OptKind
   struct Out {
     float *entity = nullptr, *relation = nullptr, *modulus = nullptr, *losses = nullptr;
   } out;
@@ -426,6 +432,24 @@ AdamT adam_t(const kge_adam_desc* adam, const kge_adam_tensor* t) {
   o.step_size = o.p ? t->step_size : 0.f;
   o.bc2s = o.p ? t->bias_correction2_sqrt : 1.f;
   return o;
+}
+
+// Adagrad's descriptor in the fields the argument builders read (OptKind,
+// kge_device.h): state_sum where exp_avg stands, lr as step_size.  exp_avg_sq
+// repeats state_sum so the shared non-NULL and alignment checks see every
+// streamed array; no kernel reads it.
+kge_adam_desc adagrad_view(const kge_adagrad_desc& d) {
+  kge_adam_desc v;
+  memset(&v, 0, sizeof(v));
+  auto tensor = [&](const kge_adagrad_tensor& t) {
+    return kge_adam_tensor{t.param, t.state_sum, t.state_sum, d.lr, 1.f};
+  };
+  v.entity = tensor(d.entity);
+  v.relation = tensor(d.relation);
+  v.modulus = tensor(d.modulus);
+  v.eps = d.eps;
+  v.write_grad = d.write_grad;
+  return v;
 }
 
 // the optimizer's part of a gradient pass's arguments
@@ -601,6 +625,7 @@ struct StepPlan {
   // min(E, B·n + 2B) of the touched rows) in place of the table's E rows
   bool lazy;
   int64_t places;
+  int opt;  // OptKind of the fused step (Adagrad: the lazy step only)
 };
 
 int plan_step(const StepCall& c, const Batch& b, const RowArgs& ra, StepPlan* out) {
@@ -620,6 +645,9 @@ int plan_step(const StepCall& c, const Batch& b, const RowArgs& ra, StepPlan* ou
   p.ents.e_begin = c.e_begin;
   p.ents.e_end = c.e_end < 0 ? m->nentity : c.e_end;
   p.ents.nsl = p.wide ? WIDE_PARTS : entity_slices(geo, b.B, m->entity_dim);
+  // row-wise Adagrad needs a whole row's Σg² in one wave: the row-per-wave pass
+  if (c.opt == OPT_ADAGRAD_ROW) p.ents.nsl = 0;
+  p.opt = c.opt;
   p.ents.reg_relations = c.reg_relations != 0;
   p.ent_parts = m->nentity * p.ents.per();
   p.rel_fused = p.all && p.ents.nsl > 0 && !p.wide;
@@ -699,11 +727,11 @@ int rows_phase(const Batch& b, const StepPlan& p, const RowArgs& ra, const CsrAr
   if (p.rel_side) {
     hipEventRecord(sd->epi_done, s);
     hipStreamWaitEvent(ss, sd->epi_done, 0);
-    st = launch_status(launch_rel_rows(rl, ss));
+    st = launch_status(launch_rel_rows(rl, ss, p.opt));
     if (st) return st;
     hipEventRecord(sd->rel_done, ss);
   } else if (!p.all) {
-    st = launch_status(launch_rel_rows(rl, s));
+    st = launch_status(launch_rel_rows(rl, s, p.opt));
     if (st) return st;
   }
   if (p.timed && !p.all) g_timer.pad_after(s, TM_EPI_END);
@@ -717,12 +745,12 @@ int entity_phase(const Batch& b, const StepPlan& p, const EntArgs& ea, const Rel
   if (p.sd && p.use_csr) hipStreamWaitEvent(s, p.sd->csr_done, 0);  // join 1: the entity pass reads the CSR
   if (p.timed) g_timer.mark(s);
   if (ea.e_end > ea.e_begin) {
-    st = launch_status(ops_for(b.m->model).entity(b.kmode, b.geo.vec, b.geo.ns, ea, s));
+    st = launch_status(ops_for(b.m->model).entity(b.kmode, b.geo.vec, b.geo.ns, ea, p.opt, s));
     if (st) return st;
   } else if (p.rel_fused) {
     // an owner with no entity rows (a trailing rank of a small table) still
     // owes the relation pass the entity launch would have carried
-    st = launch_status(launch_rel_rows(rl, s));
+    st = launch_status(launch_rel_rows(rl, s, p.opt));
     if (st) return st;
   }
   if (p.timed) g_timer.mark(s);
@@ -736,11 +764,11 @@ int finalize_phase(const Batch& b, const StepPlan& p, const RelArgs& rl, const F
   if (p.rel_side) {
     hipStreamWaitEvent(s, p.sd->rel_done, 0);  // join 2: everything the side stream wrote
   } else if (p.all && !p.rel_fused) {
-    st = launch_status(launch_rel_rows(rl, s));
+    st = launch_status(launch_rel_rows(rl, s, p.opt));
     if (st) return st;
   }
   if (p.fin_wanted && !p.fin_fused) {
-    st = launch_status(launch_finalize(fa, s));
+    st = launch_status(launch_finalize(fa, s, p.opt));
     if (st) return st;
   }
   if (p.timed) g_timer.mark(s);
@@ -802,7 +830,9 @@ Batch batch_of(const StepCall& c, const Geom& geo, const Negatives& neg, const G
           as_stream(c.ws.stream), LazyWs{}};
 }
 
-int train_impl(const StepCall& c) {
+int train_impl(const StepCall& call) {
+  StepCall c = call;
+  kge_adam_desc view;  // (kge_train_step_adagrad: c.adam once the descriptor has passed)
   const kge_model_desc* m = c.in.m;
   Geom geo;
   int st = check_model(m, &geo);
@@ -825,6 +855,20 @@ int train_impl(const StepCall& c) {
       return KGE_ERR_ARG;  // the update is in place on the model's own tables
     if (m->model == KGE_PROTATE && adam->modulus.param && adam->modulus.param != m->modulus) return KGE_ERR_ARG;
   }
+  if (const kge_adagrad_desc* ag = c.adagrad) {
+    if (ag->struct_size != (int32_t)sizeof(kge_adagrad_desc)) return KGE_ERR_ABI;
+    if (!ag->entity.param || !ag->entity.state_sum || !ag->relation.param || !ag->relation.state_sum)
+      return KGE_ERR_ARG;
+    if (ag->entity.param != m->entity_embedding || ag->relation.param != m->relation_embedding) return KGE_ERR_ARG;
+    if (m->model == KGE_PROTATE && ag->modulus.param && (ag->modulus.param != m->modulus || !ag->modulus.state_sum))
+      return KGE_ERR_ARG;
+    if (!(ag->eps > 0.f)) return KGE_ERR_ARG;  // (NaN too) eps = 0: an untouched all-zero row is NaN under the dense rule
+    if (!(ag->lr >= 0.f) || isinf(ag->lr)) return KGE_ERR_ARG;
+    if (ag->entity_rowwise != 0 && ag->entity_rowwise != 1) return KGE_ERR_ARG;
+    view = adagrad_view(*ag);
+    c.adam = &view;
+    c.opt = ag->entity_rowwise ? OPT_ADAGRAD_ROW : OPT_ADAGRAD;
+  }
   if (c.lazy) {
     // the lazy step's own refusals, behind the optimizer descriptor's (a
     // missing entity tensor is refused there): a whole single-process step
@@ -834,7 +878,14 @@ int train_impl(const StepCall& c) {
     if (c.loss.regularization != 0.f) return KGE_ERR_ARG;
     if (geo.ns == 0) return KGE_ERR_DIM;
   }
-  if (!grad_streams_aligned(geo, c.lazy ? nullptr : c.out.entity, c.out.relation, c.adam)) return KGE_ERR_ARG;
+  {
+    // (the row-wise entity state is one float per row, read and written by scalar accesses)
+    kge_adam_desc streamed{};
+    if (c.adam) streamed = *c.adam;
+    if (c.opt == OPT_ADAGRAD_ROW) streamed.entity.exp_avg = streamed.entity.exp_avg_sq = nullptr;
+    if (!grad_streams_aligned(geo, c.lazy ? nullptr : c.out.entity, c.out.relation, c.adam ? &streamed : nullptr))
+      return KGE_ERR_ARG;
+  }
   StepCall::Loss loss = c.loss;
   if (!loss.uni_weight && !loss.subsampling_weight) return KGE_ERR_ARG;
   if (m->model == KGE_PROTATE && !c.out.modulus && c.xstage != XS_ROWS_ONLY && !csr_only) return KGE_ERR_ARG;
@@ -1781,6 +1832,27 @@ int kge_train_step_lazy(const kge_model_desc* m, int32_t mode, const int64_t* po
   return train_impl(c);
 }
 
+size_t kge_train_adagrad_workspace_bytes(const kge_model_desc* m, int64_t batch, int64_t nneg) {
+  return kge_train_lazy_workspace_bytes(m, batch, nneg);
+}
+
+int kge_train_step_adagrad(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
+                           int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
+                           int32_t uni_weight, int64_t uni_batch, int32_t adversarial, float adversarial_temperature,
+                           float regularization, const kge_adagrad_desc* opt, float* grad_entity,
+                           float* grad_relation, float* grad_modulus, float* losses_out, void* workspace,
+                           size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  if (!opt) return KGE_ERR_ARG;
+  StepCall c;
+  c.in = {m, mode, pos, neg, batch, nneg};
+  c.ws = {workspace, workspace_bytes, err_flag, stream};
+  c.loss = {subsampling_weight, weight_sum, uni_weight, uni_batch, adversarial, adversarial_temperature, regularization};
+  c.adagrad = opt;
+  c.out = {grad_entity, grad_relation, grad_modulus, losses_out};
+  c.lazy = true;
+  return train_impl(c);
+}
+
 int kge_train_step_grads(const kge_model_desc* m, int32_t mode, const int64_t* pos, const int64_t* neg,
                          int64_t batch, int64_t nneg, const float* subsampling_weight, const float* weight_sum,
                          int32_t uni_weight, int64_t uni_batch, int32_t adversarial,
@@ -2027,7 +2099,7 @@ int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh
     case KGE_SHIP_ENTITY:
       if (own.e_end > own.e_begin) {
         const EntArgs ea = ent_args(b, own, sh->g, reg, grad_entity, opt_for(adam, adam ? &adam->entity : nullptr));
-        st = launch_status(op.entity(kmode, geo.vec, geo.ns, ea, s));
+        st = launch_status(op.entity(kmode, geo.vec, geo.ns, ea, OPT_ADAM, s));
         if (st) return st;
       }
       return launch_status(launch_finalize(
@@ -2048,6 +2120,15 @@ int kge_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
   if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq)) return KGE_ERR_ARG;
   return launch_status(launch_adam(param, grad, exp_avg, exp_avg_sq, numel, beta1, beta2, eps, step_size,
                                    bias_correction2_sqrt, as_stream(stream)));
+}
+
+int kge_adagrad_step(float* param, const float* grad, float* state_sum, int64_t numel, float lr, float eps,
+                     void* stream) {
+  if (!param || !grad || !state_sum || numel < 0) return KGE_ERR_ARG;
+  if (!(eps > 0.f) || !(lr >= 0.f) || isinf(lr)) return KGE_ERR_ARG;
+  if (numel == 0) return KGE_OK;
+  if (!aligned16(param) || !aligned16(grad) || !aligned16(state_sum)) return KGE_ERR_ARG;
+  return launch_status(launch_adagrad(param, grad, state_sum, numel, lr, eps, as_stream(stream)));
 }
 
 size_t kge_rank_workspace_bytes(const kge_model_desc* m, int64_t nq) {

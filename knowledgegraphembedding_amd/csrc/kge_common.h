@@ -86,10 +86,12 @@ int launch_csr(const CsrArgs& a, hipStream_t s);
 size_t touched_rows_temp_bytes(int64_t E);
 int launch_touched_rows(const int32_t* off, int64_t E, int32_t* rows, int32_t* nrows, void* tmp, size_t tmp_bytes,
                         hipStream_t s);
-int launch_rel_rows(const RelArgs& a, hipStream_t s);
-int launch_finalize(const FinArgs& a, hipStream_t s);
+// opt (OptKind): the fused optimizer's rule where the arguments carry one
+int launch_rel_rows(const RelArgs& a, hipStream_t s, int opt = OPT_ADAM);
+int launch_finalize(const FinArgs& a, hipStream_t s, int opt = OPT_ADAM);
 int launch_weight_sum(const float* w, int64_t n, float* out, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps,
                 float step_size, float bc2s, hipStream_t s);
+int launch_adagrad(float* p, const float* g, float* sum, int64_t n, float lr, float eps, hipStream_t s);
 
 }  // namespace kge

@@ -91,6 +91,14 @@ __global__ __launch_bounds__(256) void k_rel_rows(RelArgs a) {
   if (rr >= a.R) return;
   rel_row_chunks<4, true>(a, rr, lane);
 }
+// ... with the fused Adagrad step (kge_train_step_adagrad where the entity pass
+// is the row-per-wave one and carries no relation rows)
+__global__ __launch_bounds__(256) void k_rel_rows_adagrad(RelArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rr = (int64_t)blockIdx.x * 4 + wave_id();
+  if (rr >= a.R) return;
+  rel_row_chunks<4, true, OPT_ADAGRAD>(a, rr, lane);
+}
 
 // ------------------------------------------------------------ finalise
 // Loss scalars (model.py:279-297) and d/dmodulus.  One workgroup, fixed
@@ -98,6 +106,10 @@ __global__ __launch_bounds__(256) void k_rel_rows(RelArgs a) {
 __global__ __launch_bounds__(1024) void k_finalize(FinArgs a) {
   __shared__ float red[6 * 1024];
   finalize_block<1024>(a, red);
+}
+__global__ __launch_bounds__(1024) void k_finalize_adagrad(FinArgs a) {
+  __shared__ float red[6 * 1024];
+  finalize_block<1024, OPT_ADAGRAD>(a, red);
 }
 
 // Same fixed order as k_row's / k_build_q's in-kernel Σw (block_weight_sum,
@@ -159,6 +171,41 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     float P = p[i], Mv = m[i], Vv = v[i];
     adam_elem(P, g[i], Mv, Vv, k, step_size, bc2s);
     p[i] = P; m[i] = Mv; v[i] = Vv;
+  }
+}
+
+// Standalone dense element-wise Adagrad over one tensor (KGEAdagrad.step /
+// kge_adagrad_step): k_adam's shape, three streams in place of four.
+template <bool NT, int U>
+__global__ __launch_bounds__(256) void k_adagrad(float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ sum, int64_t n, float lr, float eps) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 P[U], G[U], S[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < n4) {
+        P[u] = ld4<NT>(p, i); G[u] = ld4<NT>(g, i); S[u] = ld4<NT>(sum, i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i >= n4) continue;
+      adagrad_elem(P[u].x, G[u].x, S[u].x, lr, eps);
+      adagrad_elem(P[u].y, G[u].y, S[u].y, lr, eps);
+      adagrad_elem(P[u].z, G[u].z, S[u].z, lr, eps);
+      adagrad_elem(P[u].w, G[u].w, S[u].w, lr, eps);
+      st4<NT>(p, i, P[u]);
+      st4<NT>(sum, i, S[u]);
+    }
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float P = p[i], S = sum[i];
+    adagrad_elem(P, g[i], S, lr, eps);
+    p[i] = P; sum[i] = S;
   }
 }
 
@@ -241,13 +288,16 @@ int launch_touched_rows(const int32_t* off, int64_t E, int32_t* rows, int32_t* n
                               BucketNonEmpty{off}, s);
 }
 
-int launch_rel_rows(const RelArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_rel_rows, dim3((unsigned)((a.R + 3) / 4)), dim3(256), 0, s, a);
+int launch_rel_rows(const RelArgs& a, hipStream_t s, int opt) {
+  const dim3 grid((unsigned)((a.R + 3) / 4));
+  if (opt == OPT_ADAM) hipLaunchKernelGGL(k_rel_rows, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_rel_rows_adagrad, grid, dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 
-int launch_finalize(const FinArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, a);
+int launch_finalize(const FinArgs& a, hipStream_t s, int opt) {
+  if (opt == OPT_ADAM) hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, s, a);
+  else hipLaunchKernelGGL(k_finalize_adagrad, dim3(1), dim3(1024), 0, s, a);
   return (int)hipGetLastError();
 }
 
@@ -264,6 +314,12 @@ int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float b
   // FB15k table against 5.0-5.2 for plain float4 (profiles/r01/adam_rate_variants.jsonl)
   const dim3 grid(grid_for((n + 3) / 4, 8192));
   hipLaunchKernelGGL((k_adam<true, 2>), grid, dim3(256), 0, s, p, g, m, v, n, k, step_size, bc2s);
+  return (int)hipGetLastError();
+}
+
+int launch_adagrad(float* p, const float* g, float* sum, int64_t n, float lr, float eps, hipStream_t s) {
+  const dim3 grid(grid_for((n + 3) / 4, 8192));  // (launch_adam's shape; not measured on its own)
+  hipLaunchKernelGGL((k_adagrad<true, 2>), grid, dim3(256), 0, s, p, g, sum, n, lr, eps);
   return (int)hipGetLastError();
 }
 

@@ -279,6 +279,24 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   p = p + (-step_size) * (m / denom);
 }
 
+// The fused optimizer of a gradient pass, a compile-time parameter of the lazy
+// entity kernels and of the relation / finalisation code they carry.  Adagrad
+// rides in Adam's argument fields, so no argument block changes: AdamT.p the
+// parameter, AdamT.m the state (state_sum; OPT_ADAGRAD_ROW's entity table: one
+// float per row), AdamT.step_size = lr, AdamK.eps = eps; AdamT.v and the rest
+// are not read.
+enum OptKind : int { OPT_ADAM = 0, OPT_ADAGRAD = 1, OPT_ADAGRAD_ROW = 2 };
+
+// Adagrad (kge_hip.h, kge_train_step_adagrad): one rounding per operation.
+//   s' = s + g·g;  std = sqrt(s') + eps;  p' = p + (-lr)·(g / std)
+__device__ __forceinline__ float adagrad_move(float p, float g, float std_, float lr) {
+  return p + (-lr) * (g / std_);
+}
+__device__ __forceinline__ void adagrad_elem(float& p, float g, float& s, float lr, float eps) {
+  s = s + g * g;
+  p = adagrad_move(p, g, sqrtf(s) + eps, lr);
+}
+
 // ------------------------------------------------------------ model math
 // q construction for the element (a, b) of one slot.
 //   TAIL/SINGLE: inputs (x = head, r); HEAD: inputs (r, x = tail)

@@ -443,7 +443,7 @@ enum class RefStage : int {
 struct ModelOps {
   int (*score)(int mode, int vec, int ns, const ScoreArgs&, int64_t units, hipStream_t);
   int (*row)(int mode, int vec, int ns, RowStage, const RowArgs&, size_t lds, hipStream_t);
-  int (*entity)(int mode, int vec, int ns, const EntArgs&, hipStream_t);
+  int (*entity)(int mode, int vec, int ns, const EntArgs&, int opt, hipStream_t);  // opt: OptKind
   int (*rank)(int mode, int vec, int ns, const RankArgs&, hipStream_t);
   int (*rank_tile)(int mode, int gather, const TileArgs&, hipStream_t);
   int (*rank_ref)(int mode, RefStage, const RefArgs&, hipStream_t);

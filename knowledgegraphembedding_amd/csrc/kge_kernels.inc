@@ -914,7 +914,12 @@ __global__ __launch_bounds__(256) void k_ship_chain(RowArgs a) {
 // touched rows instead of e_begin + place; a place at or past *nrows has no row
 // and returns before it reads or writes anything.  Everything after the row is
 // chosen is the dense pass's, so a touched row's bits are too.
-template <int M, int MODE, int VEC, int NS, bool LAZY = false>
+// OPT (OptKind, the LAZY instantiations of kge_train_step_adagrad): the fused
+// step is Adagrad's, element-wise (the state streamed like one Adam moment) or
+// row-wise (one state float per row: the row's Σg² is reduced lane-local over
+// the lane's elements in slot order, a then b per element as the regulariser's
+// partial is, then wave_sum; lane 0 writes G').
+template <int M, int MODE, int VEC, int NS, bool LAZY = false, int OPT = OPT_ADAM>
 __global__ __launch_bounds__(256, 3) void k_entity(EntArgs a) {
   constexpr bool CPLX = Traits<M>::cplx;
   using R_ = Row<NS, VEC, CPLX>;
@@ -1031,6 +1036,50 @@ __global__ __launch_bounds__(256, 3) void k_entity(EntArgs a) {
     if (lane == 0) a.reg_partial[e] = part;
   }
   if (a.write_grad) store_row<NS, VEC, CPLX>(a.grad_ent + e * a.Le, a.eg, lane, acc);
+  if constexpr (OPT != OPT_ADAM) {
+    if (!a.adam.p) return;
+    const float lr = a.adam.step_size, eps = a.adamk.eps;
+    float std_row = 0.f;
+    if constexpr (OPT == OPT_ADAGRAD_ROW) {
+      float part = 0.f;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        if (lane + 64 * k >= a.eg.S) continue;  // (a slot past the row's end)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          part += acc.a[k][v] * acc.a[k][v];
+          if constexpr (CPLX) part += acc.b[k][v] * acc.b[k][v];
+        }
+      }
+      part = wave_sum(part);
+      const float G = a.adam.m[e] + part / (float)a.Le;
+      if (lane == 0) a.adam.m[e] = G;
+      std_row = sqrtf(G) + eps;
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const int slot = lane + 64 * k;
+      if (slot >= a.eg.S) continue;
+#pragma unroll
+      for (int h2 = 0; h2 < (CPLX ? 2 : 1); ++h2) {
+        const int64_t off = e * a.Le + (h2 ? a.eg.half : 0) + slot * VEC;
+        float sv[VEC], pv[VEC];
+        if constexpr (OPT == OPT_ADAGRAD) ldv<VEC>(a.adam.m + off, sv);
+        ldv<VEC>(es + (h2 ? QP : 0) + slot * VEC, pv);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          float g;
+          if constexpr (CPLX) g = h2 ? acc.b[k][v] : acc.a[k][v];
+          else g = acc.a[k][v];
+          if constexpr (OPT == OPT_ADAGRAD) adagrad_elem(pv[v], g, sv[v], lr, eps);
+          else pv[v] = adagrad_move(pv[v], g, std_row, lr);
+        }
+        stv<VEC>(a.adam.p + off, pv);
+        if constexpr (OPT == OPT_ADAGRAD) stv<VEC>(a.adam.m + off, sv);
+      }
+    }
+    return;
+  }
   if (a.adam.p) {
     // fused dense Adam on this row (optimizer.step(), model.py:303)
 #pragma unroll
@@ -1091,8 +1140,14 @@ __device__ __forceinline__ void stv_nt(float* __restrict__ p, const float (&x)[4
 // gather / stream waves.
 // LAZY: as in k_entity — the block's entity group addresses rows[] (same block
 // → (slice, group) → XCD mapping, same leading blocks).
-template <int M, int MODE, bool QSL = false, bool LAZY = false>
+// OPT: OPT_ADAGRAD streams the element-wise state in the place of Adam's two
+// moments (two arrays per row where Adam streams three) and its leading blocks
+// apply the same rule to the relation rows and the modulus.  The row-wise kind
+// needs a whole row's Σg², which no block of this kernel holds: it runs
+// k_entity (plan_step).
+template <int M, int MODE, bool QSL = false, bool LAZY = false, int OPT = OPT_ADAM>
 __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
+  static_assert(OPT == OPT_ADAM || OPT == OPT_ADAGRAD, "the sliced pass has no row-wise kind");
   constexpr bool CPLX = Traits<M>::cplx;
   using EL = Elem<M, MODE>;
   constexpr int VEC = 4;
@@ -1109,12 +1164,12 @@ __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
   if (blockIdx.x < lead) {
     if (a.fin_fused && blockIdx.x == 0) {
       __shared__ float fred[6 * 256];
-      finalize_block<256>(a.fin, fred);
+      finalize_block<256, OPT>(a.fin, fred);
       return;
     }
     const int64_t rb = (int64_t)blockIdx.x - (a.fin_fused ? 1 : 0);
     const int64_t rr = rb * 4 + w;
-    if (rb < a.rel_blocks && rr < a.rel.R) rel_row_chunks<4>(a.rel, rr, lane);
+    if (rb < a.rel_blocks && rr < a.rel.R) rel_row_chunks<4, false, OPT>(a.rel, rr, lane);
     return;
   }
   const unsigned bx = blockIdx.x - lead;
@@ -1165,7 +1220,7 @@ __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
     for (int h2 = 0; h2 < H2; ++h2) {
       const int64_t off = e * a.Le + (h2 ? a.eg.half : 0) + so;
       ldv_nt(a.adam.m + off, mv[h2]);
-      ldv_nt(a.adam.v + off, vv[h2]);
+      if constexpr (OPT == OPT_ADAM) ldv_nt(a.adam.v + off, vv[h2]);
     }
   }
   auto ld_slot = [&](const float* row, float (&x)[VEC], float (&y)[VEC]) {
@@ -1290,11 +1345,14 @@ __global__ __launch_bounds__(256) void k_entity_sl(EntArgs a) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         pv[v] = h2 ? eb[v] : ea[v];
-        adam_elem(pv[v], h2 ? accb[v] : acca[v], mv[h2][v], vv[h2][v], a.adamk, a.adam.step_size, a.adam.bc2s);
+        if constexpr (OPT == OPT_ADAM)
+          adam_elem(pv[v], h2 ? accb[v] : acca[v], mv[h2][v], vv[h2][v], a.adamk, a.adam.step_size, a.adam.bc2s);
+        else
+          adagrad_elem(pv[v], h2 ? accb[v] : acca[v], mv[h2][v], a.adam.step_size, a.adamk.eps);
       }
       stv_nt(a.adam.p + off, pv);
       stv_nt(a.adam.m + off, mv[h2]);
-      stv_nt(a.adam.v + off, vv[h2]);
+      if constexpr (OPT == OPT_ADAM) stv_nt(a.adam.v + off, vv[h2]);
     }
   }
 }
@@ -3210,11 +3268,21 @@ struct Launch {
     return (int)hipGetLastError();
   }
   // column-sliced pass for float4 rows; the row-per-wave pass otherwise
-  static int entity(const EntArgs& a, hipStream_t s) {
+  // opt (OptKind): the fused optimizer's rule; Adagrad only with the lazy rows
+  static int entity(const EntArgs& a, int opt, hipStream_t s) {
+    if (opt != OPT_ADAM && !a.rows) return -1;
     if constexpr (VEC == 4) {
       if (a.nsl > 0) {
         const int64_t ne = a.e_end - a.e_begin;  // (lazy: the row places, kge_capi.hip run_grad)
         const unsigned gs = (unsigned)(a.nsl * ((ne + 3) / 4)) + ent_lead_blocks(a);
+        if (opt == OPT_ADAGRAD) {
+          if (a.q_sl)
+            hipLaunchKernelGGL((k_entity_sl<M, MODE, true, true, OPT_ADAGRAD>), dim3(gs), dim3(256), 0, s, a);
+          else
+            hipLaunchKernelGGL((k_entity_sl<M, MODE, false, true, OPT_ADAGRAD>), dim3(gs), dim3(256), 0, s, a);
+          return (int)hipGetLastError();
+        }
+        if (opt != OPT_ADAM) return -1;  // (the row-wise kind is planned unsliced)
         if (a.rows) {
           if (a.q_sl)
             hipLaunchKernelGGL((k_entity_sl<M, MODE, true, true>), dim3(gs), dim3(256), 0, s, a);
@@ -3230,6 +3298,14 @@ struct Launch {
       }
     }
     const unsigned grid = (unsigned)((a.e_end - a.e_begin + 3) / 4);
+    if (opt == OPT_ADAGRAD) {
+      hipLaunchKernelGGL((k_entity<M, MODE, VEC, NS, true, OPT_ADAGRAD>), dim3(grid), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    }
+    if (opt == OPT_ADAGRAD_ROW) {
+      hipLaunchKernelGGL((k_entity<M, MODE, VEC, NS, true, OPT_ADAGRAD_ROW>), dim3(grid), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    }
     if (a.rows) {
       hipLaunchKernelGGL((k_entity<M, MODE, VEC, NS, true>), dim3(grid), dim3(256), 0, s, a);
       return (int)hipGetLastError();
@@ -3296,7 +3372,7 @@ struct RunScore { static int run(const ScoreArgs& a, int64_t u, hipStream_t s) {
 template <int M, int MODE, int VEC, int NS>
 struct RunRow { static int run(RowStage stage, const RowArgs& a, size_t l, hipStream_t s) { return Launch<M, MODE, VEC, NS>::row(stage, a, l, s); } };
 template <int M, int MODE, int VEC, int NS>
-struct RunEntity { static int run(const EntArgs& a, hipStream_t s) { return Launch<M, MODE, VEC, NS>::entity(a, s); } };
+struct RunEntity { static int run(const EntArgs& a, int opt, hipStream_t s) { return Launch<M, MODE, VEC, NS>::entity(a, opt, s); } };
 template <int M, int MODE, int VEC, int NS>
 struct RunRank { static int run(const RankArgs& a, hipStream_t s) { return Launch<M, MODE, VEC, NS>::rank(a, s); } };
 
@@ -3325,8 +3401,8 @@ struct ModelTable {
   static int row(int mode, int vec, int ns, RowStage stage, const RowArgs& a, size_t l, hipStream_t s) {
     return dispatch<M, RunRow>(mode, vec, ns, stage, a, l, s);
   }
-  static int entity(int mode, int vec, int ns, const EntArgs& a, hipStream_t s) {
-    return dispatch<M, RunEntity>(mode, vec, ns, a, s);
+  static int entity(int mode, int vec, int ns, const EntArgs& a, int opt, hipStream_t s) {
+    return dispatch<M, RunEntity>(mode, vec, ns, a, opt, s);
   }
   static int rank(int mode, int vec, int ns, const RankArgs& a, hipStream_t s) {
     return dispatch<M, RunRank>(mode, vec, ns, a, s);

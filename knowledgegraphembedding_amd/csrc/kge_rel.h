@@ -14,7 +14,9 @@ namespace kge {
 // P4: four occurrence rows in flight (the standalone k_rel_rows; the trailing
 // blocks of k_entity_sl keep one, so the entity pass's register budget is
 // not set by this path)
-template <int U, bool P4 = false>
+// OPT: the fused optimizer's rule (OptKind; Adagrad is element-wise here
+// whatever the entity table's kind)
+template <int U, bool P4 = false, int OPT = OPT_ADAM>
 __device__ __forceinline__ void rel_row_chunks(const RelArgs& a, int64_t rr, int lane) {
   // the rows of this relation: its CSR bucket (ascending occurrence ids)
   const int32_t b0 = a.off[a.E + rr], b1 = a.off[a.E + rr + 1];
@@ -87,11 +89,19 @@ __device__ __forceinline__ void rel_row_chunks(const RelArgs& a, int64_t rr, int
       if (a.adam.p) {
         float* P = a.adam.p + rr * a.Lr + k0;
         float* Mm = a.adam.m + rr * a.Lr + k0;
-        float* Vv = a.adam.v + rr * a.Lr + k0;
-        for (int e = 0; e < nel; ++e) {
-          float pv = x[e], mv = Mm[e], vv = Vv[e];
-          adam_elem(pv, acc[u][e], mv, vv, a.adamk, a.adam.step_size, a.adam.bc2s);
-          P[e] = pv; Mm[e] = mv; Vv[e] = vv;
+        if constexpr (OPT == OPT_ADAM) {
+          float* Vv = a.adam.v + rr * a.Lr + k0;
+          for (int e = 0; e < nel; ++e) {
+            float pv = x[e], mv = Mm[e], vv = Vv[e];
+            adam_elem(pv, acc[u][e], mv, vv, a.adamk, a.adam.step_size, a.adam.bc2s);
+            P[e] = pv; Mm[e] = mv; Vv[e] = vv;
+          }
+        } else {
+          for (int e = 0; e < nel; ++e) {
+            float pv = x[e], sv = Mm[e];
+            adagrad_elem(pv, acc[u][e], sv, a.adam.step_size, a.adamk.eps);
+            P[e] = pv; Mm[e] = sv;
+          }
         }
       }
     }
@@ -108,7 +118,7 @@ __device__ __forceinline__ void rel_row_chunks(const RelArgs& a, int64_t rr, int
 // as a 1024-wide tree whatever NT is: the levels o >= NT in registers, the
 // rest in LDS — so k_finalize (NT = 1024) and the entity launch's fused last
 // block (NT = 256) produce identical bits.  red: [6][NT] floats of LDS.
-template <int NT>
+template <int NT, int OPT = OPT_ADAM>
 __device__ __forceinline__ void finalize_block(const FinArgs& a, float* red) {
   constexpr int V = 1024, K = V / NT;
   const int tid = threadIdx.x;
@@ -184,9 +194,15 @@ __device__ __forceinline__ void finalize_block(const FinArgs& a, float* red) {
     }
     if (a.grad_modulus) a.grad_modulus[0] = tot[5];
     if (a.adam.p) {  // pRotatE modulus, fused optimizer step
-      float pv = a.adam.p[0], mv = a.adam.m[0], vv = a.adam.v[0];
-      adam_elem(pv, tot[5], mv, vv, a.adamk, a.adam.step_size, a.adam.bc2s);
-      a.adam.p[0] = pv; a.adam.m[0] = mv; a.adam.v[0] = vv;
+      if constexpr (OPT == OPT_ADAM) {
+        float pv = a.adam.p[0], mv = a.adam.m[0], vv = a.adam.v[0];
+        adam_elem(pv, tot[5], mv, vv, a.adamk, a.adam.step_size, a.adam.bc2s);
+        a.adam.p[0] = pv; a.adam.m[0] = mv; a.adam.v[0] = vv;
+      } else {
+        float pv = a.adam.p[0], sv = a.adam.m[0];
+        adagrad_elem(pv, tot[5], sv, a.adam.step_size, a.adamk.eps);
+        a.adam.p[0] = pv; a.adam.m[0] = sv;
+      }
     }
   }
 }

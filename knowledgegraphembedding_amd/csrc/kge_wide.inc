@@ -487,8 +487,8 @@ struct Launch<M, MODE, 1, 0> {
     }
     return (int)hipGetLastError();
   }
-  static int entity(const EntArgs& a, hipStream_t s) {
-    if (a.nsl < 1) return -1;
+  static int entity(const EntArgs& a, int opt, hipStream_t s) {
+    if (a.nsl < 1 || opt != OPT_ADAM) return -1;  // (the lazy steps refuse wide rows)
     const int64_t units = (a.e_end - a.e_begin) * (int64_t)a.nsl;
     hipLaunchKernelGGL((k_entity_w<M, MODE>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);
     return (int)hipGetLastError();

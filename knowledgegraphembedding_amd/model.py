@@ -381,22 +381,28 @@ class KGEModel(nn.Module):
 
     # --------------------------------------------------------------- training
     def _check_lazy(self, optimizer, args):
-        """A lazy optimizer (KGELazyAdam) has one step, fused into the gradient
-        passes of a single process; refuse every other configuration before
-        anything is launched.  Returns whether `optimizer` is lazy."""
+        """A lazy optimizer (KGELazyAdam, KGEAdagrad) has one step, fused into
+        the gradient passes of a single process; refuse every other
+        configuration before anything is launched, naming the optimizer passed.
+        Returns whether `optimizer` is lazy."""
         if not getattr(optimizer, 'lazy_entity', False):
             return False
+        who = self._lazy_name(optimizer)
         if getattr(self, 'row_partition', None) is not None:
-            raise ValueError("KGELazyAdam (lazy entity Adam) does not run with a row partition")
+            raise ValueError(f"{who} does not run with a row partition")
         if getattr(args, 'dp_group', None) is not None:
-            raise ValueError("KGELazyAdam (lazy entity Adam) does not run with a data-parallel group")
+            raise ValueError(f"{who} does not run with a data-parallel group")
         if not self.fuse_optimizer:
-            raise ValueError("KGELazyAdam (lazy entity Adam) exists only fused into the train step: "
+            raise ValueError(f"{who} exists only fused into the train step: "
                              "model.fuse_optimizer must be True")
         if float(args.regularization) != 0.0:
-            raise ValueError("KGELazyAdam (lazy entity Adam) takes no regulariser: the L3 gradient is dense "
+            raise ValueError(f"{who} takes no regulariser: the L3 gradient is dense "
                              "(-r / --regularization must be 0)")
         return True
+
+    @staticmethod
+    def _lazy_name(optimizer):
+        return getattr(optimizer, 'lazy_name', "KGELazyAdam (lazy entity Adam)")
 
     def _grad_buffers(self, lazy=False):
         """(grad_entity, grad_relation, grad_modulus, losses); a lazy step has
@@ -444,10 +450,12 @@ class KGEModel(nn.Module):
         range's all-reduce there, overlapping the next range's computation).
         With a KGELazyAdam `optimizer` the step is kge_train_step_lazy: the
         entity table's update covers the rows the batch touches, no [E, Le]
-        gradient buffer exists and entity_embedding.grad stays None."""
+        gradient buffer exists and entity_embedding.grad stays None.
+        With a KGEAdagrad `optimizer` it is kge_train_step_adagrad: the same
+        lazy step with the Adagrad rule, which equals the dense update."""
         lazy = self._check_lazy(optimizer, args)
         if lazy and entity_chunks is not None:
-            raise ValueError("KGELazyAdam (lazy entity Adam) takes no entity chunks (a data-parallel path)")
+            raise ValueError(f"{self._lazy_name(optimizer)} takes no entity chunks (a data-parallel path)")
         dev = ops._require_device(self.entity_embedding)
         g, rng = self._host_scalars()
         ge, gr, gm, losses = self._grad_buffers(lazy)
@@ -458,8 +466,11 @@ class KGEModel(nn.Module):
             adam = optimizer.prepare_fused(self.entity_embedding, self.relation_embedding, self._modulus(),
                                            write_grad=self.keep_grads)
         if lazy and adam is None:
-            raise ValueError("KGELazyAdam (lazy entity Adam): the optimizer does not fit the fused step (it must "
-                             "hold the model's own contiguous tables with one betas / eps setting)")
+            raise ValueError(f"{self._lazy_name(optimizer)}: the optimizer does not fit the fused step (it must "
+                             f"hold the model's own contiguous tables with one {optimizer.fused_setting} setting)")
+        adagrad = None
+        if isinstance(adam, _lib.AdagradDesc):
+            adam, adagrad = None, adam
         kw = dict(adversarial=bool(args.negative_adversarial_sampling),
                   temperature=float(getattr(args, 'adversarial_temperature', 1.0)),
                   uni_weight=bool(args.uni_weight), regularization=float(args.regularization),
@@ -468,7 +479,7 @@ class KGEModel(nn.Module):
         desc = self.desc()
         if entity_chunks is None:
             ops.train_step_grads(desc, mode, positive_sample, negative_sample, subsampling_weight, dev, adam=adam,
-                                 lazy=lazy, **kw)
+                                 lazy=lazy, adagrad=adagrad, **kw)
         else:
             run = lambda **x: ops.train_step_grads(desc, mode, positive_sample, negative_sample,  # noqa: E731
                                                    subsampling_weight, dev, **kw, **x)

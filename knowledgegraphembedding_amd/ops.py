@@ -214,16 +214,25 @@ def train_step_grads(desc: _lib.ModelDesc, mode: str, pos: torch.Tensor, neg: to
                      grad_modulus: Optional[torch.Tensor],
                      losses: torch.Tensor, weight_sum_dev: Optional[torch.Tensor] = None,
                      uni_batch: int = 0, adam: Optional[_lib.AdamDesc] = None, phases: int = _lib.PHASE_ALL,
-                     entity_range: Optional[tuple] = None, lazy: bool = False) -> None:
+                     entity_range: Optional[tuple] = None, lazy: bool = False,
+                     adagrad: Optional[_lib.AdagradDesc] = None) -> None:
     """Fused scoring + loss + backward into the given dense grad buffers (model.py:252-301);
     with `adam`, also the optimizer step, fused into the gradient passes (model.py:303).
     `phases` / `entity_range` run a part of the step (kge_train_step_grads_phased): the
     data-parallel path reduces entity-row chunks while later chunks are computed.
     `lazy` (with `adam`, whole step only): kge_train_step_lazy — the entity table's Adam
-    covers the rows the batch touches; `grad_entity` is not used and may be None."""
+    covers the rows the batch touches; `grad_entity` is not used and may be None.
+    `adagrad` (instead of `adam`, whole step only): kge_train_step_adagrad — the lazy step
+    with the fused Adagrad rule, which on the touched rows alone is the dense update."""
     if mode not in ("head-batch", "tail-batch"):
         raise ValueError("Training batch mode %s not supported" % mode)
-    if lazy and (adam is None or phases != _lib.PHASE_ALL or entity_range is not None):
+    if adagrad is not None:
+        if adam is not None:
+            raise ValueError("adam= and adagrad= are mutually exclusive")
+        if phases != _lib.PHASE_ALL or entity_range is not None:
+            raise ValueError("the Adagrad train step is a whole step")
+        lazy = True
+    elif lazy and (adam is None or phases != _lib.PHASE_ALL or entity_range is not None):
         raise ValueError("the lazy train step is a whole step with a fused optimizer (adam=...)")
     if grad_entity is None and not lazy:
         raise ValueError("grad_entity is required (only the lazy train step has no entity gradient)")
@@ -238,7 +247,9 @@ def train_step_grads(desc: _lib.ModelDesc, mode: str, pos: torch.Tensor, neg: to
               int(bool(uni_weight)), int(uni_batch), int(bool(adversarial)), float(temperature), float(regularization))
     tail = (_ptr(grad_entity), grad_relation.data_ptr(), _ptr(grad_modulus), losses.data_ptr(), ws.data_ptr(),
             ws.numel(), st.err.data_ptr(), _stream(dev))
-    if lazy:
+    if adagrad is not None:
+        _lib.check(lib.kge_train_step_adagrad(*common, adagrad, *tail), "kge_train_step_adagrad")
+    elif lazy:
         _lib.check(lib.kge_train_step_lazy(*common, adam, *tail), "kge_train_step_lazy")
     elif phases != _lib.PHASE_ALL or entity_range is not None:
         if adam is not None:
@@ -402,6 +413,24 @@ def adam_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, ex
         _lib.load().kge_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                   param.numel(), beta1, beta2, eps, step_size, bc2_sqrt, _stream(dev)),
         "kge_adam_step",
+    )
+
+
+def adagrad_step(param: torch.Tensor, grad: torch.Tensor, state_sum: torch.Tensor, *, lr: float,
+                 eps: float) -> None:
+    """One dense element-wise Adagrad update of one tensor (kge_adagrad_step; the rule in kge_hip.h)."""
+    if not eps > 0.0 or not lr >= 0.0 or math.isinf(lr):
+        raise ValueError("adagrad_step needs eps > 0 and a finite lr >= 0")
+    dev = _require_device(param, grad, state_sum)
+    for t in (param, grad, state_sum):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError("adagrad tensors must be contiguous float32")
+    if grad.numel() != param.numel() or state_sum.numel() != param.numel():
+        raise ValueError("adagrad tensors must have the parameter's size")
+    _lib.check(
+        _lib.load().kge_adagrad_step(param.data_ptr(), grad.data_ptr(), state_sum.data_ptr(), param.numel(),
+                                     float(lr), float(eps), _stream(dev)),
+        "kge_adagrad_step",
     )
 
 

@@ -1,6 +1,7 @@
 """KGEAdam — torch.optim.Adam's update as one fused HIP kernel per tensor;
 KGELazyAdam — the same with the entity table updated only in the rows a batch
-touches.
+touches; KGEAdagrad — Adagrad fused into the lazy step, where updating the
+touched rows alone is the dense update.
 
 The reference optimises with a plain torch.optim.Adam(lr) (run.py:266-269,
 re-created on every learning-rate decay, run.py:315-322).  KGEAdam keeps that
@@ -20,6 +21,7 @@ from . import ops
 
 class KGEAdam(torch.optim.Optimizer):
     lazy_entity = False  # KGELazyAdam: the fused step updates touched entity rows only
+    fused_setting = "betas / eps"  # what prepare_fused needs equal across the tables' groups
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
         if weight_decay != 0 or amsgrad:
@@ -164,3 +166,112 @@ class KGELazyAdam(KGEAdam):
     step() has nothing left to do for that table."""
 
     lazy_entity = True
+    lazy_name = "KGELazyAdam (lazy entity Adam)"  # as KGEModel's refusals name it
+
+
+class KGEAdagrad(torch.optim.Optimizer):
+    """Adagrad fused into the lazy train step (kge_train_step_adagrad).
+
+    The rule (include/kge_hip.h), per element in fp32:
+        sum += g*g;  p += (-lr) * (g / (sqrt(sum) + eps))
+    is torch.optim.Adagrad's with lr_decay = 0, weight_decay = 0 and
+    initial_accumulator_value = 0 — the only configuration served.  A zero
+    gradient changes neither `sum` nor `p`, so the fused step, which touches
+    only the entity rows of its batch, equals the dense update on every row at
+    every step: there is no staleness as with KGELazyAdam, and the state is
+    one table instead of two.
+
+    rowwise_entity=True keeps ONE float per entity row instead (state 4*E
+    bytes): G += mean_k(g_k^2), p_k += (-lr) * (g_k / (sqrt(G) + eps)).  The
+    relation table and the pRotatE modulus stay element-wise.
+
+    State keys are 'step' and 'sum'; without rowwise_entity a state_dict loads
+    into torch.optim.Adagrad and back.  Like KGELazyAdam the step exists only
+    fused into the gradient passes of a single process (KGEModel.train_step
+    raises ValueError for a row partition, a data-parallel group,
+    model.fuse_optimizer = False or a regulariser); step() applies the dense
+    element-wise rule (kge_adagrad_step) to any other parameter with a .grad."""
+
+    lazy_entity = True
+    lazy_name = "KGEAdagrad (fused lazy Adagrad)"
+    fused_setting = "lr / eps"
+
+    def __init__(self, params, lr=1e-2, eps=1e-10, rowwise_entity=False, lr_decay=0, weight_decay=0,
+                 initial_accumulator_value=0):
+        if lr_decay != 0 or weight_decay != 0 or initial_accumulator_value != 0:
+            raise ValueError("KGEAdagrad implements lr_decay=0, weight_decay=0, initial_accumulator_value=0 only")
+        if not lr >= 0.0 or math.isinf(lr):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not eps > 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps} (must be > 0: with eps = 0 an untouched all-zero row "
+                             "would be NaN under the dense rule)")
+        defaults = dict(lr=lr, lr_decay=0, eps=eps, weight_decay=0, initial_accumulator_value=0, foreach=None,
+                        maximize=False, differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        self.rowwise_entity = bool(rowwise_entity)
+        self._fused_done = set()
+        self._rowwise = set()  # ids of the parameters whose 'sum' is one float per row
+
+    _group_of = KGEAdam._group_of
+
+    def _advance(self, p, rowwise=False):
+        state = self.state[p]
+        if len(state) == 0:
+            state['step'] = torch.tensor(0.0)
+            if rowwise:
+                state['sum'] = torch.zeros(p.shape[0], dtype=p.dtype, device=p.device)
+            else:
+                state['sum'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        state['step'] += 1
+        return state
+
+    def prepare_fused(self, entity, relation, modulus=None, write_grad=True):
+        """Adagrad descriptor for kge_train_step_adagrad.  Advances the step
+        counters now and marks the tensors so the following step() skips them.
+        Returns None if the configuration does not fit."""
+        from . import _lib
+        tensors = [entity, relation] + ([modulus] if modulus is not None else [])
+        groups = [self._group_of(p) for p in tensors]
+        if any(g is None for g in groups) or any(not p.requires_grad for p in tensors):
+            return None
+        if len({(g['lr'], g['eps']) for g in groups}) != 1:  # the descriptor carries one lr and one eps
+            return None
+        if any(not p.is_contiguous() for p in tensors):
+            return None
+        desc = _lib.AdagradDesc()
+        desc.lr, desc.eps = groups[0]['lr'], groups[0]['eps']
+        desc.entity_rowwise = 1 if self.rowwise_entity else 0
+        desc.write_grad = 1 if write_grad else 0
+        for p, field in zip(tensors, ('entity', 'relation', 'modulus')):
+            rowwise = self.rowwise_entity and field == 'entity'
+            state = self._advance(p, rowwise)
+            if state['sum'].shape != ((p.shape[0],) if rowwise else p.shape) or not state['sum'].is_contiguous():
+                raise ValueError(f"KGEAdagrad: the {field} table's 'sum' state has shape {tuple(state['sum'].shape)}; "
+                                 f"rowwise_entity={self.rowwise_entity} needs "
+                                 f"{(p.shape[0],) if rowwise else tuple(p.shape)}")
+            if rowwise:
+                self._rowwise.add(id(p))
+            t = getattr(desc, field)
+            t.param = p.data_ptr()
+            t.state_sum = state['sum'].data_ptr()
+            self._fused_done.add(id(p))
+        return desc
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        done, self._fused_done = self._fused_done, set()
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.grad is None or id(p) in done:
+                    continue
+                if id(p) in self._rowwise or ('sum' in self.state[p] and self.state[p]['sum'].shape != p.shape):
+                    raise ValueError("KGEAdagrad: a row-wise entity table has no dense step (its .grad must stay None; "
+                                     "the update exists only fused into the train step)")
+                state = self._advance(p)
+                grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                ops.adagrad_step(p.data, grad, state['sum'], lr=group['lr'], eps=group['eps'])
+        return loss

@@ -10,7 +10,8 @@ Differences from the reference, all on the execution side:
     --cuda is implied when a GPU is present and required otherwise);
   * the optimizer is KGEAdam (torch.optim.Adam's update, fused), state-dict
     compatible with the reference's checkpoints (KGE_ENTITY_ADAM=lazy in the
-    environment: KGELazyAdam, which updates only the entity rows a batch touches);
+    environment: KGELazyAdam, which updates only the entity rows a batch touches;
+    KGE_OPTIMIZER=adagrad | adagrad_rowwise: KGEAdagrad, fused into the lazy step);
   * under torchrun (WORLD_SIZE > 1) every rank trains on its own -b batch and
     gradients are all-reduced over RCCL (knowledgegraphembedding_amd.distributed);
     rank 0 logs, validates and saves.
@@ -18,6 +19,7 @@ Differences from the reference, all on the execution side:
 from __future__ import absolute_import, division, print_function
 
 import argparse
+import functools
 import json
 import logging
 import os
@@ -28,7 +30,7 @@ from torch.utils.data import DataLoader
 
 from .dataloader import BidirectionalOneShotIterator, RankShardSampler, TrainDataset
 from .model import KGEModel
-from .optim import KGEAdam, KGELazyAdam
+from .optim import KGEAdagrad, KGEAdam, KGELazyAdam
 
 
 def adam_class():
@@ -43,6 +45,29 @@ def adam_class():
     if kind == 'lazy':
         return KGELazyAdam
     raise ValueError("KGE_ENTITY_ADAM=%s not supported (dense or lazy)" % kind)
+
+
+def optimizer_class():
+    """The optimizer factory of a run, from the environment variable
+    KGE_OPTIMIZER: "adam" (default) what adam_class() picks; "adagrad"
+    KGEAdagrad, the fused lazy Adagrad step (single GPU, no regulariser; equal
+    to the dense Adagrad update, with one state table instead of Adam's two);
+    "adagrad_rowwise" the same with one state float per entity row.
+    KGE_ENTITY_ADAM is read only when the optimizer is Adam: a non-default
+    value beside an Adagrad optimizer is refused.  Not a flag: the command
+    line is the reference's.  Called at the start and at every learning-rate
+    decay, where the reference re-creates its optimizer with zero state."""
+    kind = os.environ.get('KGE_OPTIMIZER', 'adam')
+    if kind == 'adam':
+        return adam_class()
+    if kind not in ('adagrad', 'adagrad_rowwise'):
+        raise ValueError("KGE_OPTIMIZER=%s not supported (adam, adagrad or adagrad_rowwise)" % kind)
+    if os.environ.get('KGE_ENTITY_ADAM', 'dense') != 'dense':
+        raise ValueError("KGE_ENTITY_ADAM=%s is an Adam setting; KGE_OPTIMIZER=%s does not read it"
+                         % (os.environ['KGE_ENTITY_ADAM'], kind))
+    if kind == 'adagrad':
+        return KGEAdagrad
+    return functools.partial(KGEAdagrad, rowwise_entity=True)
 
 
 _FLAG = dict(action='store_true')
@@ -359,7 +384,7 @@ def main(args):
         train_iterator = make_train_iterator(args, train_triples, nentity, nrelation, rank, world)
     if args.do_train:
         current_learning_rate = args.learning_rate
-        optimizer = adam_class()(trainable(), lr=current_learning_rate)
+        optimizer = optimizer_class()(trainable(), lr=current_learning_rate)
         warm_up_steps = args.warm_up_steps if args.warm_up_steps else args.max_steps // 2
 
     if args.init_checkpoint:
@@ -403,7 +428,7 @@ def main(args):
             if step >= warm_up_steps:
                 current_learning_rate = current_learning_rate / 10
                 logging.info('Change learning_rate to %f at step %d' % (current_learning_rate, step))
-                optimizer = adam_class()(trainable(), lr=current_learning_rate)
+                optimizer = optimizer_class()(trainable(), lr=current_learning_rate)
                 warm_up_steps = warm_up_steps * 3
             if step % args.save_checkpoint_steps == 0:
                 osd = optimizer_state()
