@@ -13,8 +13,8 @@
  *     row-major and contiguous.  Embeddings are fp32, indices int64 — the
  *     reference's own dtypes (model.py:45,52; dataloader.py:63-65).
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).
- *     Nothing here allocates, frees or synchronises: every call is
- *     graph-capturable.  Scratch comes from a caller-owned workspace whose
+ *     Nothing here allocates, frees or synchronises: every call is meant to
+ *     be graph-capturable (what is pinned: "Graph capture" below).  Scratch comes from a caller-owned workspace whose
  *     size the matching *_workspace_bytes() query returns.  The workspace
  *     must be 256-byte aligned (what hipMalloc gives): its sub-buffers sit at
  *     256-byte offsets from its base and are read 16 bytes at a time.  A
@@ -25,6 +25,40 @@
  *     a poisoned workspace of exactly the queried size; the end of the
  *     training layout is not written at its shapes, so there the exact size
  *     is exercised but a short one would not be noticed).
+ *   - Graph capture (tests/test_graph_gpu.py).  A call captured on `stream`
+ *     reads every DEVICE pointer's contents at replay: tables, ids, filter
+ *     lists, weights and optimizer state may be overwritten in place between
+ *     replays.  Every by-value argument and every descriptor's contents are
+ *     those of the capture: kge_adam_desc / kge_adagrad_desc scalars
+ *     (step_size and bias_correction2_sqrt: a captured Adam step replays with
+ *     the bias corrections of the step it was captured at), kge_adam_step's
+ *     and kge_adagrad_step's scalars, kge_sample_negatives' key, the ranking
+ *     `flags` / path, kge_topk's k and parts, phase ranges, sizes.  Environment
+ *     switches (KGE_RANK_SIDE, KGE_CSR_SERIAL, ...) are read at capture.  The
+ *     stage timers (kge_stage_timer) must be off.  A first call may be
+ *     captured cold: the side stream and its events are created inside the
+ *     capture if need be (pinned for kge_rank_filtered_ex under
+ *     KGE_RANK_SIDE=1 and kge_topk with k = 128 in a fresh process).
+ *     Pinned against eager calls, bit for bit, on two input sets and repeated
+ *     replays: kge_score, kge_rank_filtered_ex (every path, KGE_RANK_SIDE=1,
+ *     KGE_RANK_REUSE_TABLE after a call of the same graph),
+ *     kge_rank_filtered_both, kge_topk, kge_rank_candidates,
+ *     kge_rank_relations, kge_sample_negatives, kge_adam_step,
+ *     kge_adagrad_step.  These zero their counters and bitmaps with a kernel:
+ *     a captured hipMemsetAsync replayed a stale fill pattern.
+ *     NOT pinned: kge_score_backward, the kge_train_* family and
+ *     kge_ship_step.  Their occurrence CSR still zeroes its bucket counts with
+ *     hipMemsetAsync, and one captured factor-exchange program ended in a GPU
+ *     memory fault whose cause was not established; treat their capture as
+ *     unsupported.  Their multi-call protocols would in any case have to be
+ *     captured whole, because the side stream forks in one call and joins in
+ *     another: KGE_PHASE_ROWS forks, KGE_PHASE_ENTITY / KGE_PHASE_FINALIZE
+ *     join; KGE_SHIP_ROWS forks, KGE_SHIP_CHAIN joins.  (kge_train_csr and
+ *     kge_train_csr_range run on the caller's stream alone.)  A fork or join
+ *     edge the runtime refuses is returned as KGE_ERR_HIP_BASE + hipError_t by
+ *     the ranking and by kge_ship_step; the kge_train_* phases do not check
+ *     theirs yet.  pRotatE's three-call ranking form has a host sin between
+ *     its calls and cannot be one graph.
  *   - Return value: 0 on success, a KGE_ERR_* code for argument errors
  *     (checked on the host before anything is launched), or a hipError_t
  *     (offset by KGE_ERR_HIP_BASE) if a launch fails.

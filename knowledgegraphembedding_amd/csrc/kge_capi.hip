@@ -248,6 +248,12 @@ Side* side_for_device() {
   return &sd;
 }
 
+// One edge of a fork or join.  The status is the caller's to return: under
+// stream capture an edge the runtime refuses would otherwise leave a graph
+// that races, reported as KGE_OK.
+int edge_record(hipEvent_t ev, hipStream_t s) { return hip_status(hipEventRecord(ev, s)); }
+int edge_wait(hipStream_t s, hipEvent_t ev) { return hip_status(hipStreamWaitEvent(s, ev, 0)); }
+
 // ================================================================ training
 
 struct GradWs {
@@ -1310,12 +1316,12 @@ int rank_queries(RankRun& r, Side* rsd) {
   if (rp == RP_MFMA) {
     // (q of both directions split in one launch: the tile is mode-independent)
     st = launch_status(launch_split_bf16(w.q, nqt, m->entity_dim, w.qs, s));
-    if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
+    if (!st && rsd) st = edge_wait(s, rsd->rk_join);  // join: everything below reads the table's work
     if (!st && !r.true_ref)
       st = launch_status(launch_rank_mfma_x(1, w.qs, w.es, nqt, m->nentity, m->entity_dim, w.true_id, w.s_true,
                                             w.bits, w.gt, r.win, s));
   } else {
-    if (rsd) hipStreamWaitEvent(s, rsd->rk_join, 0);  // join: everything below reads the table's work
+    if (rsd && (st = edge_wait(s, rsd->rk_join))) return st;  // join: everything below reads the table's work
     if (rp == RP_MFMA32)
       st = launch_status(launch_rank_mfma(1, w.q, m->entity_embedding, nqt, m->nentity, m->entity_dim, w.true_id,
                                           w.s_true, w.bits, w.gt, r.win, s));
@@ -1364,13 +1370,11 @@ int rank_queries(RankRun& r, Side* rsd) {
 int rank_fast(RankRun& r) {
   g_rank_timer.mark(r.s, 0, r.ndir);  // (rank timer) 0: the call starts
   Side* rsd = env_int("KGE_RANK_SIDE", 0) != 0 ? side_for_device() : nullptr;
-  if (rsd) {
-    hipEventRecord(rsd->rk_fork, r.s);
-    hipStreamWaitEvent(rsd->s, rsd->rk_fork, 0);
-  }
-  int st = rank_table(r, rsd ? rsd->s : r.s);
+  int st;
+  if (rsd && ((st = edge_record(rsd->rk_fork, r.s)) || (st = edge_wait(rsd->s, rsd->rk_fork)))) return st;
+  st = rank_table(r, rsd ? rsd->s : r.s);
   if (st) return st;
-  if (rsd) hipEventRecord(rsd->rk_join, rsd->s);
+  if (rsd && (st = edge_record(rsd->rk_join, rsd->s))) return st;
   return rank_queries(r, rsd);
 }
 
@@ -1516,7 +1520,7 @@ int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
   if (st) return st;
   // 2. the excluded candidates as a bitmap (state stands in for the true id: negative, no bit)
   if (!filt_off)
-    st = hip_status(hipMemsetAsync(w.bits, 0, (size_t)nq * W * sizeof(uint32_t), s));
+    st = launch_status(launch_zero(w.bits, nq * W, s));
   else if (ftab)
     st = launch_status(launch_filter_bits_tab(w.qsan, mode == KGE_HEAD_BATCH ? 1 : 0, filt_off, filt_ids, w.state, nq,
                                               m->nentity, m->nrelation, w.bits, err_flag, s));
@@ -1609,7 +1613,7 @@ int rank_cand_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries
   a.nslot = cand_slots(a.Le);
   a.in_place = a.nslot == 0;
   a.qref = w.qref; a.gt = w.gt; a.eq = w.eq; a.err = err_flag;
-  st = hip_status(hipMemsetAsync(w.gt, 0, (size_t)(2 * nq) * sizeof(int32_t), s));
+  st = launch_status(launch_zero(w.gt, 2 * nq, s));  // (gt | eq)
   if (st) return st;
   st = launch_status(ops_for(m->model).rank_cand(kernel_mode(mode), a, s));
   if (st) return st;
@@ -1692,7 +1696,7 @@ int rank_rel_impl(const kge_model_desc* m, const int64_t* queries, int64_t nq, c
   a.nslot = rel_slots(a.Le);
   a.in_place = a.nslot == 0;
   a.scores = scores_out; a.gt = w.gt; a.eq = w.eq; a.err = err_flag;
-  st = hip_status(hipMemsetAsync(w.gt, 0, (size_t)(2 * nq) * sizeof(int32_t), s));
+  st = launch_status(launch_zero(w.gt, 2 * nq, s));  // (gt | eq)
   if (st) return st;
   st = launch_status(ops_for(m->model).rank_rel(a, s));
   if (st) return st;
@@ -2077,13 +2081,10 @@ int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh
       // only this shard's rows are visited by its entity pass
       const CsrArgs ca = csr_args(b, sh->own_begin, sh->own_end);
       hipStream_t ss = sd ? sd->s : s;
-      if (sd) {
-        hipEventRecord(sd->fork, s);
-        hipStreamWaitEvent(ss, sd->fork, 0);
-      }
+      if (sd && ((st = edge_record(sd->fork, s)) || (st = edge_wait(ss, sd->fork)))) return st;
       st = launch_status(launch_csr(ca, ss));
       if (st) return st;
-      if (sd) hipEventRecord(sd->csr_done, ss);
+      if (sd && (st = edge_record(sd->csr_done, ss))) return st;
       const size_t lds = row_lds(geo, m->entity_dim, ra, false);  // (wide rows: refused by the launch)
       if (lds > LDS_MAX) return KGE_ERR_DIM;
       return launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipRows, ra, lds, s));
@@ -2093,7 +2094,7 @@ int kge_ship_step(const kge_model_desc* m, int32_t mode, const kge_ship_desc* sh
     case KGE_SHIP_CHAIN:
       st = launch_status(op.row(kmode, geo.vec, geo.ns, RowStage::ShipChain, ra, 0, s));
       if (st) return st;
-      if (sd) hipStreamWaitEvent(s, sd->csr_done, 0);  // the relation pass reads the CSR
+      if (sd && (st = edge_wait(s, sd->csr_done))) return st;  // the relation pass reads the CSR
       return launch_status(launch_rel_rows(
           rel_args(b, own.reg_relations ? 3.f * reg : 0.f, m->nentity * own.per(), grad_relation, OPT_GRAD_ONLY), s));
     case KGE_SHIP_ENTITY:

@@ -80,6 +80,10 @@ int launch_rel_trig_table(const float* rel, int64_t R, int Lr, float kappa, floa
 // kge_topk's reduction of every query's `parts` partial lists (kge_common.hip)
 int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
                       int64_t* ids_out, float* scores_out, hipStream_t s);
+// `words` 32-bit words at p set to zero by a kernel of this library (kge_common.hip).  Not
+// hipMemsetAsync: captured into a graph, its memset node filled the counters with a stale 16-byte
+// pattern on a later replay (tests/test_graph_gpu.py), where a kernel node replays its arguments.
+int launch_zero(void* p, int64_t words, hipStream_t s);
 size_t csr_scan_temp_bytes(int64_t nb);
 int launch_csr(const CsrArgs& a, hipStream_t s);
 // the non-empty entity buckets of the CSR offsets `off`, ascending, into rows[0 .. *nrows) (device)

@@ -216,6 +216,17 @@ static inline unsigned grid_for(int64_t n, unsigned cap = 4096) {
   return (unsigned)(g < cap ? g : cap);
 }
 
+// Zeroed counters and bitmaps (see launch_zero in kge_common.h).
+__global__ __launch_bounds__(256) void k_zero(uint32_t* __restrict__ p, int64_t words) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) p[i] = 0u;
+}
+
+int launch_zero(void* p, int64_t words, hipStream_t s) {
+  if (words <= 0) return 0;
+  hipLaunchKernelGGL(k_zero, dim3(grid_for(words, 1024)), dim3(256), 0, s, static_cast<uint32_t*>(p), words);
+  return (int)hipGetLastError();
+}
+
 // Bucket offsets: a device-wide exclusive scan of cnt[0..nb] (cnt[nb] = 0, so
 // off[nb] = total) — rocPRIM's decoupled look-back scan, integer and exact;
 // its scratch comes from the caller's workspace.

@@ -883,8 +883,7 @@ int launch_filter_bits(const int64_t* filt_off, const int64_t* filt_ids, const i
                        filt_off, filt_ids, true_id, nq, E, (int64_t)0, (int)W, bits, err, nullptr, nullptr, nullptr);
     return (int)hipGetLastError();
   }
-  hipError_t he = hipMemsetAsync(bits, 0, (size_t)nq * W * 4, s);
-  if (he != hipSuccess) return (int)he;
+  if (int z = launch_zero(bits, nq * W, s)) return z;
   hipLaunchKernelGGL(k_filter_bits, dim3(4, (unsigned)nq), dim3(256), 0, s, filt_off, filt_ids, true_id, nq, E, W,
                      bits, err);
   return (int)hipGetLastError();
@@ -899,8 +898,7 @@ int launch_filter_bits_tab(const int64_t* queries, int head, const int64_t* tab,
                        nullptr, vals, true_id, nq, E, R, (int)W, bits, err, nullptr, nullptr, nullptr);
     return (int)hipGetLastError();
   }
-  hipError_t he = hipMemsetAsync(bits, 0, (size_t)nq * W * 4, s);
-  if (he != hipSuccess) return (int)he;
+  if (int z = launch_zero(bits, nq * W, s)) return z;
   hipLaunchKernelGGL(k_filter_bits_tab, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, queries, head, tab, vals,
                      true_id, nq, E, R, W, bits, err);
   return (int)hipGetLastError();
