@@ -59,6 +59,17 @@
  *     the ranking and by kge_ship_step; the kge_train_* phases do not check
  *     theirs yet.  pRotatE's three-call ranking form has a host sin between
  *     its calls and cannot be one graph.
+ *   - Large entity tables (tests/test_big_table_gpu.py).  Pinned on tables of
+ *     2.16e9, 4.32e9 and 8.60e9 bytes (past 2^31 bytes, 2^32 bytes and 2^31
+ *     floats), with ids on either side of each line: the ranking, top-k,
+ *     gather, training and optimizer entries.  Ranking paths by table size:
+ *     the split-bf16 MFMA tile (path 1) while its split operands stay under
+ *     0x7FFFFFF0 bytes (a table of about 2 GiB), the fp32 MFMA tile (path 4)
+ *     up to 0xFFFFFF00 table bytes, the register tile and the wave scan
+ *     (paths 2 and 3) at any size; a path the table does not admit is
+ *     KGE_ERR_ARG, and path 0 falls through them in that order.  NOT pinned:
+ *     pRotatE ranking, tables of 2^32 elements (16 GiB) and more,
+ *     kge_ship_step and the kge_train_step_from_rows* family on such tables.
  *   - Return value: 0 on success, a KGE_ERR_* code for argument errors
  *     (checked on the host before anything is launched), or a hipError_t
  *     (offset by KGE_ERR_HIP_BASE) if a launch fails.

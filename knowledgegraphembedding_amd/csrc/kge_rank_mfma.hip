@@ -65,7 +65,12 @@ struct MfmaArgs {
 // VGPRs, 3 workgroups per CU): 68 % MFMA-busy against 79 % here.
 constexpr int BK2 = 16;
 constexpr int STAGE2 = 2 * 128 * BK2;  // floats per stage: A [128][16] then B [128][16]
-constexpr uint32_t OOB2 = 0x7FFFFFF0u;
+// "No row" / "k past K" offset: past every buffer the host guards admit
+// (launch_rank_mfma and rank_path refuse operands of 0xFFFFFF00 bytes or
+// more), so the range check zeroes the load whatever the table's size, and
+// the 16-byte access does not wrap 32 bits.  0x7FFFFFF0 lay inside tables of
+// 2 to 4 GB and read their data there, which only the zero q operand hid.
+constexpr uint32_t OOB2 = 0xFFFFFF10u;
 
 template <bool GATHER>
 __global__ __launch_bounds__(256, 4) void k_rank_mfma(MfmaArgs a) {
