@@ -836,6 +836,91 @@ int kge_rank_relations(const kge_model_desc *m, const int64_t *queries, int64_t 
                        void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /*
+ * SHARDED FILTERED RANKING — the filtered ranks of kge_rank_filtered over an
+ * entity table that is split into row shards, one per rank, evaluated in place:
+ * no rank ever holds another's rows (the evaluation half of "Query shipping"
+ * above).  The conventions are kge_ship_step's: m->entity_embedding points
+ * own_begin rows BEFORE this rank's shard, m->nentity is the GLOBAL count, and
+ * only rows [own_begin, own_end) are read.  A rank is a count of candidates
+ * whose reference-order fp32 score beats the true one's, so the shards' counts
+ * sum to the single-process rank bit for bit.  One entry, three stages, each a
+ * call with the same arguments, with the host's collectives between them:
+ *   KGE_RSHARD_ROWS   fixed_rows[q] = the row of the query's fixed side (t
+ *                     head-batch, h tail-batch) where this rank owns it, all-zero
+ *                     bits elsewhere         → all-reduce(SUM) fixed_rows viewed
+ *                     as int32 (adding zero integers keeps every bit, −0.0 too).
+ *                     A fixed-side id outside [0, nentity) sets KGE_DEVERR_INDEX
+ *                     and leaves zeros.
+ *   KGE_RSHARD_TRUE   reads the reduced fixed_rows; s_true[q] = the reference-
+ *                     order score of the true triple (the bits kge_rank_candidates
+ *                     gives the true entity) where this rank owns the ranked
+ *                     entity (h head-batch, t tail-batch), zero bits elsewhere
+ *                     and for a query with an id out of range
+ *                                            → all-reduce(SUM) s_true as int32.
+ *   KGE_RSHARD_COUNT  reads the reduced fixed_rows and s_true;
+ *                     counts[0][q] = #{e in [own_begin, own_end), e != true id,
+ *                     e not in the query's filter list : score(e) > s_true[q]},
+ *                     counts[1][q] the same with ==  → all-reduce(SUM) counts
+ *                     (int64); rank = 1 + counts[0], ties = counts[1].
+ *                     A query with h, r or t out of range gets 0 / 0 and sets
+ *                     KGE_DEVERR_INDEX; the other queries proceed.  Filter-list
+ *                     ids outside the shard (or outside the table) are simply
+ *                     not this shard's: no error.
+ * "score" is the reference's fp32 score on the contract of kge_rank_candidates:
+ * every owned row is scored in the mode's reference operation order (no fast
+ * pass) — bit-exact for TransE, DistMult and ComplEx, for RotatE when
+ * m->relation_trig holds the reference's cos / sin (NULL: correctly rounded on
+ * the device), and pRotatE with the correctly rounded device sin (there is no
+ * three-call form here).
+ *   flags: 0 = filt_off [nq + 1] / filt_ids are per-query lists;
+ *   KGE_RANK_FILTER_TABLE = they are the whole filter index, as
+ *   kge_rank_filtered_ex.  Lists may be empty, repeat ids and list the true id.
+ *   own_begin == own_end is a valid empty shard: ROWS and TRUE write zeros,
+ *   COUNT writes zero counts.
+ *   Rows of any width and alignment: 16-byte slots or single floats by the
+ *   alignment rule above (of the shard's first row and the relation table;
+ *   fixed_rows, s_true and relation_trig need float alignment only); rows too
+ *   wide to stage in LDS are read in place.  Queries go on grid.x: the
+ *   65,535-query ceiling of kge_rank_filtered* does not apply, and there is no
+ *   [nq, E/32] bitmap — each workgroup builds the exclusion bits of its own
+ *   chunk of at most 1024 rows in LDS.  The counts are integer sums over the
+ *   chunks: deterministic, and independent of the launch geometry
+ *   (KGE_RANK_SHARD_CHUNK, diagnostic: rows per chunk; KGE_RANK_SHARD_QPW,
+ *   diagnostic: 2 or 4 queries share every staged row of a workgroup).
+ *   Nothing allocates or synchronises; counts is zeroed by a kernel.  Every
+ *   stage writes its output for every query, so no buffer needs clearing.
+ * Host checks, in this order: the model (as every entry); the mode (KGE_SINGLE:
+ * KGE_ERR_MODE); a NULL descriptor (KGE_ERR_ARG), then its struct_size
+ * (KGE_ERR_ABI); then KGE_ERR_ARG for a stage that is not one of the three,
+ * own_begin > own_end or a range outside [0, nentity], flags other than 0 or
+ * KGE_RANK_FILTER_TABLE, null queries / err_flag or nq < 0, and a NULL buffer
+ * of the stage (ROWS: fixed_rows; TRUE: fixed_rows, s_true; COUNT: fixed_rows,
+ * s_true, counts, filt_off, filt_ids); nq == 0 returns KGE_OK; more queries
+ * (COUNT: (chunk, query) work items) than grid.x holds (KGE_ERR_DIM); the
+ * workspace (KGE_ERR_WORKSPACE).
+ * The workspace holds the queries' q vectors when rows are read in place, and
+ * nothing otherwise (a 256-byte minimum); any stage may use any workspace.
+ * NOT pinned for this entry: graph capture, and tables past 2 GiB (row offsets
+ * are 64-bit, but no test runs it there).
+ */
+#define KGE_RSHARD_ROWS  1
+#define KGE_RSHARD_TRUE  2
+#define KGE_RSHARD_COUNT 3
+typedef struct kge_rank_shard_desc {
+  int32_t struct_size;          /* = sizeof(kge_rank_shard_desc) (else KGE_ERR_ABI) */
+  int32_t flags;                /* 0 or KGE_RANK_FILTER_TABLE */
+  int64_t own_begin, own_end;   /* global ids; own_begin == own_end is a valid empty shard */
+  float *fixed_rows;            /* [nq, entity_dim]: row of h (tail-batch) / t (head-batch) */
+  float *s_true;                /* [nq]: reference-order score of the true triple */
+  const int64_t *filt_off, *filt_ids; /* as kge_rank_filtered_ex, both forms */
+  int64_t *counts;              /* [2, nq]: row 0 strictly greater, row 1 equal */
+} kge_rank_shard_desc;
+size_t kge_rank_shard_workspace_bytes(const kge_model_desc *m, int64_t nq);
+int kge_rank_shard(const kge_model_desc *m, int32_t mode, const kge_rank_shard_desc *sh, int32_t stage,
+                   const int64_t *queries, int64_t nq, void *workspace, size_t workspace_bytes,
+                   int32_t *err_flag, void *stream);
+
+/*
  * pRotatE ranks bit-exact to the reference — whose sin (model.py:245) is its
  * CPU vector library's (ATen → MKL VML here), which no device instruction
  * sequence reproduces — in three calls on one stream and workspace:

@@ -24,6 +24,7 @@ RANK_FILTER_TABLE = 0x400  # KGE_RANK_FILTER_TABLE
 RANK_LIST_CAP = 1024  # KGE_RANK_LIST_CAP
 PHASE_ROWS, PHASE_ENTITY, PHASE_FINALIZE, PHASE_ALL = 1, 2, 4, 7
 SHIP_Q, SHIP_ROWS, SHIP_MERGE, SHIP_CHAIN, SHIP_ENTITY = 1, 2, 3, 4, 5
+RSHARD_ROWS, RSHARD_TRUE, RSHARD_COUNT = 1, 2, 3  # KGE_RSHARD_*
 ERR_HIP_BASE = 1000
 
 
@@ -95,6 +96,18 @@ class ShipDesc(C.Structure):
                 ("parts", C.c_void_p), ("scores", C.c_void_p), ("g", C.c_void_p), ("dq", C.c_void_p),
                 ("pq", C.c_void_p), ("pstats", C.c_void_p), ("ent_contrib", C.c_void_p),
                 ("rel_contrib", C.c_void_p), ("row_stats", C.c_void_p)]
+
+
+class RankShardDesc(C.Structure):
+    """struct kge_rank_shard_desc (sharded filtered ranking, kge_rank_shard; struct_size is set on construction)."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(RankShardDesc)
+
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("own_begin", C.c_int64), ("own_end", C.c_int64),
+                ("fixed_rows", C.c_void_p), ("s_true", C.c_void_p), ("filt_off", C.c_void_p),
+                ("filt_ids", C.c_void_p), ("counts", C.c_void_p)]
 
 
 _P = C.c_void_p
@@ -180,6 +193,8 @@ SIGNATURES = {
     "kge_rank_candidates": (C.c_int, [_DESC, _I32, _P, _I64, _P, _I64, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_relations_workspace_bytes": (_SZ, [_DESC, _I64]),
     "kge_rank_relations": (C.c_int, [_DESC, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "kge_rank_shard_workspace_bytes": (_SZ, [_DESC, _I64]),
+    "kge_rank_shard": (C.c_int, [_DESC, _I32, C.POINTER(RankShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
     "kge_rank_sin_args": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_finish_sin": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_stage_timer": (C.c_int, [_I32, _P, _I32]),

@@ -1704,6 +1704,87 @@ int rank_rel_impl(const kge_model_desc* m, const int64_t* queries, int64_t nq, c
   return launch_status(launch_rank_cand_emit(queries, nq, m->nentity, m->nrelation, w.gt, w.eq, ranks_out, ties_out, s));
 }
 
+// ---- sharded filtered ranking (kge_rank_shard)
+// The chunks of the owned range: equal sizes of at most SHARD_CPC_MAX rows, and
+// when the queries alone do not fill the device (256 CUs × 8 workgroups), more
+// of them, of at least 64 rows each.  KGE_RANK_SHARD_CHUNK (diagnostic): rows
+// per chunk; the counts are integer sums, so no geometry changes a result.
+int64_t shard_chunks(int64_t nq, int64_t rows, int* cpc) {
+  int64_t per = env_int("KGE_RANK_SHARD_CHUNK", 0);
+  if (per < 1) {
+    const int64_t want = (2048 + nq - 1) / nq, most = (rows + 63) / 64,
+                  least = (rows + SHARD_CPC_MAX - 1) / SHARD_CPC_MAX;
+    int64_t chunks = want < most ? want : most;
+    if (chunks < least) chunks = least;
+    per = (rows + chunks - 1) / chunks;
+  }
+  if (per > SHARD_CPC_MAX) per = SHARD_CPC_MAX;
+  *cpc = (int)per;
+  return (rows + per - 1) / per;
+}
+
+struct ShardWs {
+  float* qref;  // [nq, Le], rows read in place only
+};
+ShardWs carve_shard(void* ws, const kge_model_desc* m, int64_t nq, size_t* bytes) {
+  Carver c(ws);
+  ShardWs w;
+  w.qref = c.take<float>(shard_slots(m->entity_dim) == 0 ? nq * (int64_t)m->entity_dim : 0);
+  *bytes = c.off + 256;
+  return w;
+}
+
+int rank_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_desc* sh, int32_t stage,
+                    const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                    void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!sh) return KGE_ERR_ARG;
+  if (sh->struct_size != (int32_t)sizeof(kge_rank_shard_desc)) return KGE_ERR_ABI;
+  if (stage != KGE_RSHARD_ROWS && stage != KGE_RSHARD_TRUE && stage != KGE_RSHARD_COUNT) return KGE_ERR_ARG;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
+  if (sh->flags != 0 && sh->flags != KGE_RANK_FILTER_TABLE) return KGE_ERR_ARG;
+  if (!queries || !err_flag || nq < 0) return KGE_ERR_ARG;
+  if (!sh->fixed_rows) return KGE_ERR_ARG;
+  if (stage >= KGE_RSHARD_TRUE && !sh->s_true) return KGE_ERR_ARG;
+  if (stage == KGE_RSHARD_COUNT && (!sh->counts || !sh->filt_off || !sh->filt_ids)) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  const int64_t rows = sh->own_end - sh->own_begin;
+  int cpc = 1;
+  int64_t chunks = 1;  // (an empty shard: one chunk of no rows, which still flags the bad queries)
+  if (stage == KGE_RSHARD_COUNT && rows > 0) chunks = shard_chunks(nq, rows, &cpc);
+  if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // queries (COUNT: (chunk, query) work items) on grid.x
+  size_t need = 0;
+  const ShardWs w = carve_shard(workspace, m, nq, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  hipStream_t s = as_stream(stream);
+  ShardArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
+  a.queries = queries; a.filt_off = sh->filt_off; a.filt_ids = sh->filt_ids;
+  a.ftab = (sh->flags & KGE_RANK_FILTER_TABLE) ? 1 : 0;
+  a.nq = nq; a.E = m->nentity; a.R = m->nrelation; a.own_lo = sh->own_begin; a.own_hi = sh->own_end;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  a.c = consts_of(m);
+  a.chunks = chunks; a.cpc = cpc;
+  // 16-byte slots by the header's rule: the row span a multiple of 4, both tables aligned
+  // (rows are then a multiple of 16 bytes, so the shard is aligned as its base pointer is)
+  a.vec4 = (a.K % 4 == 0) && aligned16(m->entity_embedding) && aligned16(m->relation_embedding);
+  a.nslot = shard_slots(a.Le);
+  a.in_place = a.nslot == 0;
+  a.qw = env_int("KGE_RANK_SHARD_QPW", 1);  // (diagnostic: queries per workgroup, 2 or 4; the same counts)
+  a.fixed_rows = sh->fixed_rows; a.s_true = sh->s_true; a.qref = w.qref; a.counts = sh->counts; a.err = err_flag;
+  if (stage == KGE_RSHARD_COUNT) {
+    st = launch_status(launch_zero(sh->counts, 4 * nq, s));  // [2, nq] int64
+    if (st) return st;
+  }
+  return launch_status(ops_for(m->model).rank_shard(kernel_mode(mode), stage, a, s));
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -2225,6 +2306,20 @@ int kge_rank_relations(const kge_model_desc* m, const int64_t* queries, int64_t 
                        void* workspace, size_t workspace_bytes, int32_t* err_flag, void* stream) {
   return rank_rel_impl(m, queries, nq, filt_off, filt_ids, ranks_out, ties_out, scores_out, workspace, workspace_bytes,
                        err_flag, stream);
+}
+
+size_t kge_rank_shard_workspace_bytes(const kge_model_desc* m, int64_t nq) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0) return 0;
+  size_t b = 0;
+  carve_shard(nullptr, m, nq, &b);
+  return b;
+}
+
+int kge_rank_shard(const kge_model_desc* m, int32_t mode, const kge_rank_shard_desc* sh, int32_t stage,
+                   const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                   void* stream) {
+  return rank_shard_impl(m, mode, sh, stage, queries, nq, workspace, workspace_bytes, err_flag, stream);
 }
 
 int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,

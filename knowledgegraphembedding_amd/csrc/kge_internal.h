@@ -417,6 +417,45 @@ inline int rel_slots(int Le) {
   return k > 8 ? 8 : (k < 1 ? 0 : k);
 }
 
+// Sharded filtered ranking (kge_rank_shard; k_rshard_rows, k_rshard_true,
+// k_rshard_count).  `ent` points own_lo rows before the shard: only rows
+// [own_lo, own_hi) are read.  COUNT's work unit = (chunk of cpc consecutive owned
+// rows, query), query-minor on grid.x; counts are the caller's, zeroed by the call.
+struct ShardArgs {
+  const float* ent;
+  const float* rel;
+  const float* modulus;
+  const float* trig;         // RotatE: [R, 2, Lr] reference cos | sin of the phases, or null
+  const int64_t* queries;    // [nq, 3]
+  const int64_t* filt_off;   // per-query lists [nq + 1], or (ftab) the whole index's [E·R + 1] starts
+  const int64_t* filt_ids;
+  int ftab;                  // KGE_RANK_FILTER_TABLE
+  int64_t nq, E, R;
+  int64_t own_lo, own_hi;    // the owned rows (global ids)
+  int Le, Lr, K;             // K = reduction length (complex: Le / 2)
+  Consts c;
+  int64_t chunks;            // chunks of the owned range
+  int cpc;                   // rows per chunk (the last one may hold fewer)
+  int vec4;                  // rows staged in 16-byte slots (the header's alignment rule)
+  int nslot;                 // half-waves with an LDS row slot (shard_slots)
+  int in_place;              // rows too wide for LDS: q from qref, rows read in place
+  int qw;                    // queries per workgroup asked for (KGE_RANK_SHARD_QPW; the launch decides, and sets nslot)
+  float* fixed_rows;        // [nq, Le] the fixed side's rows (ROWS writes, TRUE / COUNT read the reduced ones)
+  float* s_true;             // [nq] (TRUE writes, COUNT reads the reduced ones)
+  float* qref;               // [nq, Le] reference-order q (in_place only; k_rshard_q writes it)
+  int64_t* counts;           // [2, nq] += strictly greater | equal
+  int32_t* err;
+};
+constexpr int SHARD_CPC_MAX = 1024;  // rows per chunk: the chunk's scores and its exclusion bitmap sit in LDS
+// half-waves with an LDS row slot: the q, largest score array and bitmap of
+// each of the workgroup's qw queries and the slots (rows rounded to 4 floats)
+// share 64 KB; 0: not even one fits (qw = 1: rows are read in place)
+inline int shard_slots(int Le, int qw = 1) {
+  const int Lp = (Le + 3) & ~3;
+  const int k = (65536 / 4 - qw * (Lp + cand_scrp(SHARD_CPC_MAX) + rel_bmw(SHARD_CPC_MAX))) / Lp;
+  return k > 8 ? 8 : (k < 1 ? 0 : k);
+}
+
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {
   Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
@@ -451,6 +490,7 @@ struct ModelOps {
   int (*topk_tile)(int mode, const TopkTileArgs&, hipStream_t);
   int (*rank_cand)(int mode, const CandArgs&, hipStream_t);
   int (*rank_rel)(const RelRankArgs&, hipStream_t);
+  int (*rank_shard)(int mode, int stage, const ShardArgs&, hipStream_t);  // stage: KGE_RSHARD_*
 };
 
 ModelOps model_ops_transe();

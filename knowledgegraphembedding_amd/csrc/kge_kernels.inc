@@ -3225,6 +3225,325 @@ int launch_rank_rel(const RelRankArgs& a, hipStream_t s) {
   return go(k_rank_rel<M, 0, 1>);
 }
 
+// ------------------------------------------- sharded filtered ranking
+// kge_rank_shard: the filtered ranks over a row shard [own_lo, own_hi) of the
+// entity table, in three stages with the host's all-reduces between them
+// (kge_hip.h).  a.ent points own_lo rows before the shard, so rows are
+// addressed by global id and only owned ones are touched; the fixed side's row
+// and the true score come from the caller's reduced buffers, never from the
+// scanned table.
+//   k_rshard_rows   a half-wave per query copies the fixed side's row (its
+//                   bits) where owned, zero bits elsewhere.
+//   k_rshard_true   a workgroup per query builds the reference q in LDS from
+//                   fixed_rows[q]; its first half-wave scores the true row where
+//                   it lies (ref_score_half, TransE included: the sequential
+//                   sum cand_score_transe_lds reproduces).
+//   k_rshard_count  k_rank_cand with a contiguous range in place of a list.
+//                   Work unit = (chunk of cpc consecutive owned rows, query),
+//                   one 256-thread workgroup each, QUERY-minor on grid.x: the
+//                   workgroups resident together scan the same chunk, whose
+//                   rows then come from L2.  The workgroup builds q, then the
+//                   exclusion bitmap of its chunk (≤ 32 words) from the query's
+//                   filter list and the true id with LDS atomics; its half-
+//                   waves walk the rows j = half, half + nslot, ... staged
+//                   through their LDS slots one row ahead.  Every row is
+//                   scored (no divergence inside a half-wave); the excluded
+//                   ones are left out when the scores are counted against
+//                   s_true[q].  The two integers go to counts by atomics.
+// Dynamic LDS of k_rshard_count, floats: [q: Lp][scores: cpc | 2 counters,
+// cand_scrp][bitmap: rel_bmw][slots: nslot × Lp] (the first three QW times over
+// with QW queries per workgroup).  Rows too wide for q and one
+// slot (in_place) are read where they lie and q comes from k_rshard_q's copy in
+// the workspace.
+
+__device__ __forceinline__ bool rshard_owned(const ShardArgs& a, int64_t e) { return e >= a.own_lo && e < a.own_hi; }
+__device__ __forceinline__ bool rshard_query_ok(const ShardArgs& a, int64_t h, int64_t r, int64_t t) {
+  return h >= 0 && h < a.E && t >= 0 && t < a.E && r >= 0 && r < a.R;
+}
+
+// the query's reference-order q from the reduced fixed-side row, element k by
+// thread k mod 256 (cand_build_q with the row given)
+template <int M, int MODE>
+__device__ __forceinline__ void rshard_build_q(const ShardArgs& a, int64_t qi, int64_t r, const Consts& c,
+                                               float* __restrict__ qo) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  const float* xr = a.fixed_rows + qi * a.Le;
+  const float* rr = a.rel + r * a.Lr;
+  const float* tr = (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr;
+  for (int k = threadIdx.x; k < a.K; k += 256) {
+    const float xa = xr[k], xb = CPLX ? xr[a.K + k] : 0.f;
+    const float ra = rr[k], rb = (M == COMPLEX) ? rr[a.K + k] : 0.f;
+    float qa, qb;
+    ref_make_q<M, MODE>(xa, xb, ra, rb, c, qa, qb, tr, k, a.K);
+    qo[k] = qa;
+    if constexpr (CPLX) qo[a.K + k] = qb;
+  }
+}
+
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rshard_rows(ShardArgs a) {
+  const int hl = threadIdx.x & 31;
+  const int64_t qi = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+  if (qi >= a.nq) return;  // (a whole half-wave)
+  const int64_t x = a.queries[qi * 3 + (MODE == HEAD_BATCH ? 2 : 0)];
+  if ((x < 0 || x >= a.E) && hl == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.fixed_rows + qi * a.Le);  // (bits, not values)
+  if (rshard_owned(a, x)) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.ent + x * a.Le);
+    for (int k = hl; k < a.Le; k += 32) out[k] = src[k];
+  } else {
+    for (int k = hl; k < a.Le; k += 32) out[k] = 0u;
+  }
+}
+
+// in_place only: q of every query into the workspace, one block per query
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rshard_q(ShardArgs a) {
+  const int64_t qi = blockIdx.x;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  if (!rshard_query_ok(a, h, r, t)) return;  // (k_rshard_count flags it)
+  rshard_build_q<M, MODE>(a, qi, r, a.c, a.qref + qi * a.Le);
+}
+
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rshard_true(ShardArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float tqs[];
+  const int tid = threadIdx.x;
+  const int64_t qi = blockIdx.x;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  const int64_t te = (MODE == HEAD_BATCH) ? h : t;
+  if (!rshard_query_ok(a, h, r, t) || !rshard_owned(a, te)) {  // (block-uniform)
+    if (tid == 0) reinterpret_cast<uint32_t*>(a.s_true)[qi] = 0u;
+    return;
+  }
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const float* qs = a.qref + qi * a.Le;
+  if (!a.in_place) {
+    rshard_build_q<M, MODE>(a, qi, r, c, tqs);
+    qs = tqs;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    const float sc = ref_score_half<M, MODE>(qs, a.ent + te * a.Le, a.K, c, tid);
+    if (tid == 0) a.s_true[qi] = sc;
+  }
+}
+
+// PQ, VW: as k_rank_cand.  QW: queries per workgroup — every staged row is
+// scored against QW consecutive queries, whose q vectors, score arrays and
+// bitmaps sit side by side in LDS (the same arithmetic per (query, row), 1 / QW
+// of the row reads; staged 16-byte rows of DistMult / ComplEx / RotatE /
+// pRotatE only: TransE's LDS sum overwrites the staged row).
+template <int M, int MODE, int PQ, int VW, int QW = 1>
+__global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float ssm[];
+  constexpr bool IN_PLACE = PQ < 0;
+  static_assert(QW == 1 || (!IN_PLACE && M != TRANSE), "several queries per workgroup: staged rows, not TransE");
+  using T = typename CandSlot<VW>::T;
+  const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
+  const int64_t groups = (a.nq + QW - 1) / QW;
+  const int64_t ch = (int64_t)blockIdx.x / groups;  // chunk-major: neighbours on grid.x scan the same rows
+  const int64_t qi0 = ((int64_t)blockIdx.x - ch * groups) * QW;
+  int64_t te[QW];
+  bool ok[QW];  // (block-uniform) a bad query's counts stay 0 / 0
+  bool any = false;
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int Le = a.Le, Lp = refine_lp(Le);
+  const int64_t e0 = a.own_lo + ch * a.cpc;  // the chunk's first row
+  const int n = (int)((a.own_hi - e0 < a.cpc) ? (a.own_hi - e0) : a.cpc);  // (0: an empty shard's one chunk)
+  const int scrp = cand_scrp(a.cpc), bmw = rel_bmw(a.cpc);
+  float* const scr0 = ssm + (IN_PLACE ? 0 : QW * Lp);   // query w: scores scr0 + w·scrp (2 counters behind them),
+  uint32_t* const bm0 = reinterpret_cast<uint32_t*>(scr0 + QW * scrp);  // bitmap bm0 + w·bmw, q at ssm + w·Lp
+  float* slots = scr0 + QW * (scrp + bmw);
+  for (int w = tid; w < QW * bmw; w += 256) bm0[w] = 0u;
+  if (tid < 2 * QW) reinterpret_cast<int*>(scr0 + (tid >> 1) * scrp + a.cpc)[tid & 1] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < QW; ++w) {
+    const int64_t qi = qi0 + w;
+    ok[w] = false;
+    te[w] = 0;
+    if (qi >= a.nq) continue;  // (the last group may be short)
+    const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+    if (!rshard_query_ok(a, h, r, t)) {
+      if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+      continue;
+    }
+    ok[w] = any = true;
+    te[w] = (MODE == HEAD_BATCH) ? h : t;
+    if constexpr (!IN_PLACE) rshard_build_q<M, MODE>(a, qi, r, c, ssm + w * Lp);
+    // the chunk's excluded rows: the true id, and the filter list's ids that fall into it
+    uint32_t* bm = bm0 + w * bmw;
+    int64_t f0, f1;
+    if (a.ftab) {  // the whole index: the query's key (k_filter_bits_tab's lookup)
+      const int64_t key = (MODE == HEAD_BATCH) ? r * a.E + t : h * a.R + r;
+      f0 = a.filt_off[key];
+      f1 = a.filt_off[key + 1];
+    } else {
+      f0 = a.filt_off[qi];
+      f1 = a.filt_off[qi + 1];
+    }
+    for (int64_t i = f0 + tid; i < f1; i += 256) {
+      const int64_t x = a.filt_ids[i] - e0;
+      if (x >= 0 && x < n) atomicOr(&bm[x >> 5], 1u << (x & 31));
+    }
+    const int64_t x = te[w] - e0;
+    if (tid == 0 && x >= 0 && x < n) atomicOr(&bm[x >> 5], 1u << (x & 31));
+  }
+  if (!any) return;
+  __syncthreads();  // q is read by every half-wave
+  const int ns = IN_PLACE ? 8 : a.nslot;
+  if (half < ns) {
+    // the half's i-th item is row j = half + ns·i of the chunk
+    auto item_row = [&](int i) -> const float* { return a.ent + (e0 + half + ns * i) * Le; };
+    auto score_item = [&](int j, float* row) __attribute__((always_inline)) {
+#pragma unroll
+      for (int w = 0; w < QW; ++w) {
+        if (QW > 1 && !ok[w]) continue;  // (its q was not built)
+        const float* qs = IN_PLACE ? a.qref + qi0 * Le : ssm + w * Lp;
+        float sc;
+        if constexpr (M == TRANSE && !IN_PLACE) sc = cand_score_transe_lds<MODE>(qs, row, a.K, c, hl);
+        else sc = ref_score_half<M, MODE>(qs, row, a.K, c, hl);
+        if (hl == 0) scr0[w * scrp + j] = sc;
+      }
+      // (the scores depend on every element of the row: the row's reads are done
+      // before the next item overwrites it)
+      asm volatile("" ::: "memory");
+    };
+    const int nit = (n - half + ns - 1) / ns;  // the half's items (≤ 0: none)
+    if constexpr (IN_PLACE) {
+      for (int i = 0; i < nit; ++i) score_item(half + ns * i, const_cast<float*>(item_row(i)));  // never written
+    } else {
+      float* const row_l = slots + half * Lp;
+      const int nT = Le / VW;
+      T* const rT = reinterpret_cast<T*>(row_l);
+      const T zero = T();
+      if constexpr (PQ > 0) {
+        T nx[PQ > 0 ? PQ : 1];
+        auto fetch = [&](int i) __attribute__((always_inline)) {
+          const T* sT = reinterpret_cast<const T*>(item_row(i));
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            nx[u] = (k < nT) ? sT[k] : zero;
+          }
+        };
+        if (nit > 0) fetch(0);
+        for (int i = 0; i < nit; ++i) {
+#pragma unroll
+          for (int u = 0; u < PQ; ++u) {
+            const int k = hl + 32 * u;
+            if (k < nT) rT[k] = nx[u];
+          }
+          if (i + 1 < nit) fetch(i + 1);
+          // the half's lanes read each other's writes: one wave's LDS operations complete in order
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l);
+        }
+      } else {
+        for (int i = 0; i < nit; ++i) {
+          const T* sT = reinterpret_cast<const T*>(item_row(i));
+          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
+            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
+            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
+                    v3 = b3 ? sT[k0 + 96] : zero;
+            rT[k0] = v0;
+            if (b1) rT[k0 + 32] = v1;
+            if (b2) rT[k0 + 64] = v2;
+            if (b3) rT[k0 + 96] = v3;
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          score_item(half + ns * i, row_l);
+        }
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < QW; ++w) {
+    if (!ok[w]) continue;
+    const float* scr = scr0 + w * scrp;
+    const uint32_t* bm = bm0 + w * bmw;
+    int* cnt_s = reinterpret_cast<int*>(scr0 + w * scrp + a.cpc);
+    const float st = a.s_true[qi0 + w];
+    int g = 0, e_ = 0;
+    for (int j = tid; j < n; j += 256) {
+      if ((bm[j >> 5] >> (j & 31)) & 1u) continue;  // the true entity itself; filtered
+      g += (scr[j] > st);
+      e_ += (scr[j] == st);
+    }
+    g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
+    e_ = (int)wave_sum((float)e_);
+    if ((tid & 63) == 0 && (g | e_)) {
+      atomicAdd(&cnt_s[0], g);
+      atomicAdd(&cnt_s[1], e_);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < QW; ++w) {
+    if (tid != w || !ok[w]) continue;  // integer sums: any order of the chunks gives the same counts
+    const int* cnt_s = reinterpret_cast<const int*>(scr0 + w * scrp + a.cpc);
+    unsigned long long* cn = reinterpret_cast<unsigned long long*>(a.counts);
+    if (cnt_s[0]) atomicAdd(&cn[qi0 + w], (unsigned long long)cnt_s[0]);
+    if (cnt_s[1]) atomicAdd(&cn[a.nq + qi0 + w], (unsigned long long)cnt_s[1]);
+  }
+}
+
+template <int M>
+int launch_rank_shard(int mode, int stage, const ShardArgs& a, hipStream_t s) {
+  const int Lp = refine_lp(a.Le);
+  auto launch = [&](auto kh, auto kt, unsigned grid, size_t lds) {
+    hipLaunchKernelGGL(pick_dir(mode, kh, kt), dim3(grid), dim3(256), lds, s, a);
+    return (int)hipGetLastError();
+  };
+  if (stage == KGE_RSHARD_ROWS)
+    return launch(k_rshard_rows<M, HEAD_BATCH>, k_rshard_rows<M, TAIL_BATCH>, (unsigned)((a.nq + 7) / 8), 0);
+  if (a.in_place) {
+    const int st = launch(k_rshard_q<M, HEAD_BATCH>, k_rshard_q<M, TAIL_BATCH>, (unsigned)a.nq, 0);
+    if (st) return st;
+  }
+  if (stage == KGE_RSHARD_TRUE)
+    return launch(k_rshard_true<M, HEAD_BATCH>, k_rshard_true<M, TAIL_BATCH>, (unsigned)a.nq,
+                  a.in_place ? 0 : sizeof(float) * (size_t)Lp);
+  if (stage != KGE_RSHARD_COUNT) return -1;
+  const int nT = a.vec4 ? a.Le >> 2 : a.Le;  // slots per row
+  // several queries per workgroup (a.qw = 2 or 4): 16-byte slots of at most 1024 floats, not TransE
+  const int qw = ((a.qw == 2 || a.qw == 4) && !a.in_place && a.vec4 && nT <= 256 && M != TRANSE) ? a.qw : 1;
+  ShardArgs b = a;
+  b.nslot = shard_slots(a.Le, qw);
+  const size_t lds = sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (qw + b.nslot)) +
+                                              qw * (cand_scrp(a.cpc) + rel_bmw(a.cpc)));
+  const unsigned grid = (unsigned)(((a.nq + qw - 1) / qw) * a.chunks);
+  auto launch_b = [&](auto kh, auto kt) {
+    hipLaunchKernelGGL(pick_dir(mode, kh, kt), dim3(grid), dim3(256), lds, s, b);
+    return (int)hipGetLastError();
+  };
+#define KGE_RSHARD_GO(PQ_, VW_) \
+  launch_b(k_rshard_count<M, HEAD_BATCH, PQ_, VW_>, k_rshard_count<M, TAIL_BATCH, PQ_, VW_>)
+#define KGE_RSHARD_GOQ(PQ_, QW_) \
+  launch_b(k_rshard_count<M, HEAD_BATCH, PQ_, 4, QW_>, k_rshard_count<M, TAIL_BATCH, PQ_, 4, QW_>)
+  if constexpr (M != TRANSE) {
+    if (qw == 2) return nT <= 128 ? KGE_RSHARD_GOQ(4, 2) : KGE_RSHARD_GOQ(8, 2);
+    if (qw == 4) return nT <= 128 ? KGE_RSHARD_GOQ(4, 4) : KGE_RSHARD_GOQ(8, 4);
+  }
+#undef KGE_RSHARD_GOQ
+  if (a.in_place) return KGE_RSHARD_GO(-1, 1);
+  if (a.vec4) {
+    if (nT <= 128) return KGE_RSHARD_GO(4, 4);
+    if (nT <= 256) return KGE_RSHARD_GO(8, 4);
+    if (nT <= 512) return KGE_RSHARD_GO(16, 4);
+    return KGE_RSHARD_GO(0, 4);
+  }
+  if (nT <= 128) return KGE_RSHARD_GO(4, 1);
+  if (nT <= 256) return KGE_RSHARD_GO(8, 1);
+  if (nT <= 512) return KGE_RSHARD_GO(16, 1);
+  return KGE_RSHARD_GO(0, 1);
+#undef KGE_RSHARD_GO
+}
+
 // ------------------------------------------------------------ dispatch
 template <int M, int MODE, int VEC, int NS>
 struct Launch {
@@ -3428,6 +3747,7 @@ struct ModelTable {
     o.topk_tile = &launch_topk_tile<M>;                                                            \
     o.rank_cand = &launch_rank_cand<M>;                                                            \
     o.rank_rel = &launch_rank_rel<M>;                                                              \
+    o.rank_shard = &launch_rank_shard<M>;                                                          \
     return o;                                                                                      \
   }                                                                                                \
   }

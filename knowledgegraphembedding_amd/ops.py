@@ -670,6 +670,96 @@ def rank_relations(desc: _lib.ModelDesc, queries: torch.Tensor, dev, filt=None,
     return (ranks, ties, out_s) if scores else (ranks, ties)
 
 
+def _rank_shard(stage: int, name: str, desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, *,
+                fixed_rows: torch.Tensor, s_true: Optional[torch.Tensor] = None, filt=None,
+                filter_table: bool = False, counts: Optional[torch.Tensor] = None,
+                relation_trig: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """One stage of kge_rank_shard on the caller's buffers (checked here: a
+    wrong-sized one is an out-of-bounds access on the device)."""
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("mode %s not supported" % mode)
+    if relation_trig is not None:
+        shape = (desc.nrelation, 2, desc.relation_dim)
+        if (tuple(relation_trig.shape) != shape or relation_trig.dtype != torch.float32
+                or not relation_trig.is_contiguous() or relation_trig.device != dev):
+            raise ValueError(f"relation_trig: expected a contiguous float32 {shape} tensor on {dev}")
+        desc = _lib.ModelDesc.from_buffer_copy(desc)
+        desc.relation_trig = relation_trig.data_ptr()
+    q = _idx(queries, dev)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"queries: {tuple(q.shape)}, expected [nq, 3]")
+    nq = q.shape[0]
+    b, e = int(own[0]), int(own[1])
+    if not 0 <= b <= e <= desc.nentity:
+        raise ValueError(f"own range [{b}, {e}) is not inside [0, {desc.nentity}]")
+
+    def buf(t, what, numel, dtype):
+        if (t is None or t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of {numel} elements on {dev}")
+        return t.data_ptr()
+
+    sh = _lib.RankShardDesc()
+    sh.own_begin, sh.own_end = b, e
+    sh.fixed_rows = buf(fixed_rows, "fixed_rows", nq * desc.entity_dim, torch.float32)
+    if stage >= _lib.RSHARD_TRUE:
+        sh.s_true = buf(s_true, "s_true", nq, torch.float32)
+    keep = None
+    if stage == _lib.RSHARD_COUNT:
+        sh.counts = buf(counts, "counts", 2 * nq, torch.int64)
+        _check_filter_shape(desc, nq, filt[0], filter_table)
+        off = _idx(filt[0], dev)
+        ids = _idx(filt[1], dev) if filt[1].numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+        keep = (off, ids)
+        sh.filt_off, sh.filt_ids = off.data_ptr(), ids.data_ptr()
+        sh.flags = _lib.RANK_FILTER_TABLE if filter_table else 0
+    lib = _lib.load()
+    st = state(dev)
+    ws = workspace if workspace is not None else st.workspace(lib.kge_rank_shard_workspace_bytes(desc, nq))
+    _lib.check(lib.kge_rank_shard(desc, _lib.MODE_IDS[mode], sh, stage, q.data_ptr(), nq, ws.data_ptr(), ws.numel(),
+                                  st.err.data_ptr(), _stream(dev)), "kge_rank_shard")
+    del keep  # (the launches are queued on the stream the caching allocator frees behind)
+
+
+def rank_shard_rows(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, fixed_rows: torch.Tensor,
+                    workspace: Optional[torch.Tensor] = None) -> None:
+    """Stage ROWS of the sharded filtered ranking (kge_rank_shard): `desc`
+    addresses the shard by GLOBAL row id (entity_embedding own[0] rows before
+    the shard, nentity the global count); `fixed_rows` [nq, entity_dim] gets the
+    row of each query's fixed side (t head-batch, h tail-batch) where
+    own = (begin, end) holds it, zero bits elsewhere.  The caller sums the
+    ranks' buffers viewed as int32 (all-reduce SUM) before the next stage."""
+    _rank_shard(_lib.RSHARD_ROWS, "rank_shard_rows", desc, mode, queries, own, dev, fixed_rows=fixed_rows,
+                workspace=workspace)
+
+
+def rank_shard_true(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, fixed_rows: torch.Tensor,
+                    s_true: torch.Tensor, relation_trig: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> None:
+    """Stage TRUE: from the reduced `fixed_rows`, s_true [nq] = the reference-
+    order score of the true triple where this shard owns the ranked entity,
+    zero bits elsewhere; summed over the ranks as int32 like fixed_rows.
+    `relation_trig` as for rank_filtered."""
+    _rank_shard(_lib.RSHARD_TRUE, "rank_shard_true", desc, mode, queries, own, dev, fixed_rows=fixed_rows,
+                s_true=s_true, relation_trig=relation_trig, workspace=workspace)
+
+
+def rank_shard_count(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, fixed_rows: torch.Tensor,
+                     s_true: torch.Tensor, filt, counts: torch.Tensor, filter_table: bool = False,
+                     relation_trig: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None) -> None:
+    """Stage COUNT: from the reduced `fixed_rows` and `s_true`, counts [2, nq]
+    int64 = this shard's unfiltered rows other than the true one scoring above
+    (row 0) and equal to (row 1) the true score.  filt = (filt_off, filt_ids):
+    per-query lists, or with `filter_table` the whole filter index
+    (FilterIndex.device_table).  Summed over the ranks (int64 SUM): rank =
+    1 + counts[0], ties = counts[1].  The device error flag is left for the
+    caller's next read (raise_on_device_error): a query with an id out of
+    range counts 0 / 0."""
+    _rank_shard(_lib.RSHARD_COUNT, "rank_shard_count", desc, mode, queries, own, dev, fixed_rows=fixed_rows,
+                s_true=s_true, filt=filt, filter_table=filter_table, counts=counts, relation_trig=relation_trig,
+                workspace=workspace)
+
+
 TOPK_MAX_K = 128  # kge_hip.h KGE_TOPK_MAX_K
 TOPK_PATHS = {"auto": 0, "tile": 2, "scan": 3}
 

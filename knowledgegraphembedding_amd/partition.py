@@ -387,6 +387,82 @@ class EntityRowPartition:
             losses[2] = (losses[0] + losses[1]) / 2 + losses[3]
         return losses
 
+    # ------------------------------------------------------------ evaluation
+    RANK_BLOCK = 8192  # queries per block of the sharded ranking: bounds fixed_rows at RANK_BLOCK × dim floats
+
+    def _own_desc(self, model):
+        """The descriptor that addresses this rank's rows by global id, and the
+        rows: the shard ("queries"), or this rank's range of the replica."""
+        if self.exchange == "queries":
+            return self._ship_model_desc(model), (self.e0, self.e1)
+        return model.desc(), (self.e0, self.e1)
+
+    def rank_queries(self, model, triples, all_true_triples, mode):
+        """Per-query filtered ranks and tie counts (numpy int64, int32), as
+        KGEModel.rank_queries, with the table evaluated IN PLACE: every rank
+        scans only its own rows (kge_rank_shard) and no rank gathers another's
+        — ``materialize()`` is not called.  Collective: every rank passes the
+        same triples and gets the same result.  Per block of RANK_BLOCK queries,
+        three all-reduces on the group: the fixed side's rows from their owners
+        and the true scores from theirs (each as int32: all but one rank add
+        zero bits, so the sum keeps the owner's bits), then the int64 counts.
+        Ranks are integer counts of rows whose reference-order fp32 score beats
+        the true one's, so the sum over the shards is the single-process rank
+        bit for bit (RotatE with the reference's rotation table, as there;
+        pRotatE with the correctly rounded device sin — test_step's library-sin
+        form needs the near-tie lists of one table and is not available sharded).
+        `all_true_triples`: a triple list or a FilterIndex."""
+        import numpy as np
+        from . import ops
+        from .filters import FilterIndex
+        dev = self.shard.device
+        index = all_true_triples if isinstance(all_true_triples, FilterIndex) else \
+            FilterIndex(all_true_triples, self.nentity, model.nrelation, device=dev)
+        q = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+        desc, own = self._own_desc(model)
+        table = index.device_table(mode, dev) if os.environ.get("KGE_RANK_FILTER_TABLE", "1") != "0" else None
+        SUM = dist.ReduceOp.SUM
+        ranks, ties = [], []
+        with torch.no_grad():
+            trig = model._rank_rotation(dev)
+            for b0 in range(0, len(q), self.RANK_BLOCK):
+                qb = q[b0:b0 + self.RANK_BLOCK]
+                nq = len(qb)
+                qd = torch.from_numpy(np.ascontiguousarray(qb)).to(dev)
+                filt = table if table is not None else tuple(torch.from_numpy(x) for x in index.filter_csr(qb, mode))
+                fixed = torch.empty(nq, self.dim, device=dev)
+                ops.rank_shard_rows(desc, mode, qd, own, dev, fixed)
+                dist.all_reduce(fixed.view(torch.int32), op=SUM, group=self.group)
+                s_true = torch.empty(nq, device=dev)
+                ops.rank_shard_true(desc, mode, qd, own, dev, fixed, s_true, relation_trig=trig)
+                dist.all_reduce(s_true.view(torch.int32), op=SUM, group=self.group)
+                counts = torch.empty(2, nq, dtype=torch.int64, device=dev)
+                ops.rank_shard_count(desc, mode, qd, own, dev, fixed, s_true, filt, counts,
+                                     filter_table=table is not None, relation_trig=trig)
+                dist.all_reduce(counts, op=SUM, group=self.group)
+                ranks.append(counts[0] + 1)
+                ties.append(counts[1])
+            r = torch.cat(ranks).cpu().numpy() if ranks else np.zeros(0, np.int64)
+            t = torch.cat(ties).cpu().numpy().astype(np.int32) if ties else np.zeros(0, np.int32)
+            ops.raise_on_device_error(dev)
+        return r, t
+
+    def test_step(self, model, test_triples, all_true_triples, args):
+        """KGEModel.test_step's filtered metrics (model.py:315-429: head-batch
+        queries, then tail-batch) from rank_queries — collective, the same
+        dict on every rank, the whole table on none."""
+        from .filters import FilterIndex, triples_array
+        from .model import _rank_metrics
+        if getattr(args, 'countries', False):
+            raise ValueError("the sharded evaluation ranks entities; --countries scores regions with forward")
+        model.eval()
+        index = FilterIndex(all_true_triples, self.nentity, model.nrelation, device=self.shard.device)
+        triples = triples_array(test_triples)
+        ranks_seq = []
+        for mode in ('head-batch', 'tail-batch'):
+            ranks_seq.extend(self.rank_queries(model, triples, index, mode)[0].tolist())
+        return _rank_metrics(ranks_seq)
+
     def put_chunk(self, c0: int, c1: int) -> None:
         """Start the all-gather of every rank's shard rows [c0, c1) (collective,
         async): rank r's rows land at stage rows r·(c1−c0) …, gather() waits and

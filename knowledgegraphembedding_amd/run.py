@@ -14,7 +14,14 @@ Differences from the reference, all on the execution side:
     KGE_OPTIMIZER=adagrad | adagrad_rowwise: KGEAdagrad, fused into the lazy step);
   * under torchrun (WORLD_SIZE > 1) every rank trains on its own -b batch and
     gradients are all-reduced over RCCL (knowledgegraphembedding_amd.distributed);
-    rank 0 logs, validates and saves.
+    rank 0 logs, validates and saves;
+  * KGE_EVAL_SHARDED=1 in the environment (with --row_partition under torchrun):
+    validation and the final evaluations rank the partitioned table in place —
+    every rank scans its own rows (EntityRowPartition.test_step, kge_rank_shard)
+    and the whole table is gathered for checkpoints only.  Unset or 0: rank 0
+    evaluates the gathered table alone, as before.  Not with --countries,
+    KGE_EVAL_CANDIDATES or KGE_EVAL_RELATIONS; pRotatE then ranks with the
+    correctly rounded device sin, not the reference library's.
 """
 from __future__ import absolute_import, division, print_function
 
@@ -290,9 +297,24 @@ def _init_distributed(args):
     return dist.get_rank()
 
 
+def eval_sharded_requested(args) -> bool:
+    """KGE_EVAL_SHARDED (unset or 0: off), refused before any launch where the
+    sharded evaluation has no form: it ranks every entity for both directions
+    and nothing else."""
+    if (os.environ.get('KGE_EVAL_SHARDED', '0') or '0') == '0':
+        return False
+    if getattr(args, 'countries', False):
+        raise ValueError('KGE_EVAL_SHARDED: --countries scores regions with forward, not a ranking over the table')
+    for var in ('KGE_EVAL_CANDIDATES', 'KGE_EVAL_RELATIONS'):
+        if (os.environ.get(var, '0') or '0') != '0':
+            raise ValueError('KGE_EVAL_SHARDED cannot be combined with %s (unset one of them)' % var)
+    return True
+
+
 def main(args):
     if (not args.do_train) and (not args.do_valid) and (not args.do_test):
         raise ValueError('one of train/val/test mode must be choosed.')
+    eval_sharded = eval_sharded_requested(args)
     if args.init_checkpoint:
         override_config(args)
     elif args.data_path is None:
@@ -359,6 +381,20 @@ def main(args):
         part = EntityRowPartition(kge_model, args.dp_group, exchange=exchange)
         logging.info('Entity rows partitioned (%s exchange): rank %d owns [%d, %d)' % (exchange, rank, part.e0,
                                                                                         part.e1))
+
+    if eval_sharded and part is None:
+        raise ValueError('KGE_EVAL_SHARDED needs a partitioned entity table (--row_partition under torchrun)')
+    if eval_sharded and args.model == 'pRotatE':
+        logging.info('KGE_EVAL_SHARDED: pRotatE ranks with the correctly rounded device sin '
+                     '(the library-sin form of test_step is not available sharded)')
+
+    def sharded_eval(title, label, triples, step):
+        # collective: every rank ranks its own rows of the table in place; rank 0 logs
+        if rank == 0:
+            logging.info('Evaluating on %s Dataset...' % title)
+        metrics = part.test_step(kge_model, triples, all_true_triples, args)
+        if rank == 0:
+            log_metrics(label, step, metrics)
 
     def trainable():
         return part.parameters() if part is not None else filter(lambda p: p.requires_grad, kge_model.parameters())
@@ -443,7 +479,9 @@ def main(args):
                     metrics[metric] = sum([log[metric] for log in training_logs]) / len(training_logs)
                 log_metrics('Training average', step, metrics)
                 training_logs = []
-            if args.do_valid and step % args.valid_steps == 0:
+            if args.do_valid and step % args.valid_steps == 0 and eval_sharded:
+                sharded_eval('Valid', 'Valid', valid_triples, step)
+            elif args.do_valid and step % args.valid_steps == 0:
                 full_table(True)
                 if rank == 0:
                     logging.info('Evaluating on Valid Dataset...')
@@ -455,9 +493,18 @@ def main(args):
         if rank == 0:
             save_model(kge_model, optimizer, {'step': step, 'current_learning_rate': current_learning_rate,
                                               'warm_up_steps': warm_up_steps}, args, osd)
-    else:
+        if eval_sharded:
+            part.release()  # the checkpoint's gathered table: the evaluations below need only the shards
+    elif not eval_sharded:
         full_table(True)
 
+    if eval_sharded:
+        for wanted, title, triples, label in ((args.do_valid, 'Valid', valid_triples, 'Valid'),
+                                              (args.do_test, 'Test', test_triples, 'Test'),
+                                              (args.evaluate_train, 'Training', train_triples, 'Test')):
+            if wanted:
+                sharded_eval(title, label, triples, step)
+        return
     if rank != 0:
         return
     # final evaluations (the training split is logged under 'Test', as in the reference)
