@@ -921,6 +921,84 @@ int kge_rank_shard(const kge_model_desc *m, int32_t mode, const kge_rank_shard_d
                    int32_t *err_flag, void *stream);
 
 /*
+ * SHARDED TOP-K LINK PREDICTION — kge_topk over an entity table that is split
+ * into row shards, one per rank, predicted in place: no rank ever holds
+ * another's rows.  The conventions are kge_rank_shard's: m->entity_embedding
+ * points own_begin rows BEFORE this rank's shard, m->nentity is the GLOBAL
+ * count, and only rows [own_begin, own_end) are read.  The order (score
+ * descending, id ascending) is total and a pair's score does not depend on the
+ * launch geometry, so the merged result equals kge_topk's on the whole table
+ * with the same path, ids and score bits.  One entry, two stages, with the
+ * host's collectives around them, per block of queries:
+ *   1. kge_rank_shard(KGE_RSHARD_ROWS)   → all-reduce(SUM) fixed_rows as int32
+ *      (its kernel reads the fixed side only: the predicted column may be -1);
+ *   2. KGE_TSHARD_LIST    reads the reduced fixed_rows; list_scores / list_ids
+ *      [nq, k] = the k best unexcluded rows of [own_begin, own_end) per query,
+ *      sorted by (score descending, id ascending), with GLOBAL ids.  Unused
+ *      places — fewer than k candidates in the shard, an empty shard, a bad
+ *      query — hold score -inf and id INT32_MAX: the padding loses to every
+ *      candidate in the merge, whichever rank it comes from.
+ *                          → all-gather both into [world, nq, k], rank-major;
+ *   3. KGE_TSHARD_MERGE   reduces the `world` lists of every query in the same
+ *      order into ids_out / scores_out [nq, k] as kge_topk writes them: padding
+ *      becomes id -1 / score -inf, a bad query id -1 / score NaN.  Badness is
+ *      recomputed from `queries`, so it is the same on every rank.
+ * LIST builds q from fixed_rows[q] and the relation row with kge_topk's own
+ * arithmetic (device cos / sin; the same row bits give the same q bits), the
+ * exclusion bitmap over the shard's own rows only (nq × ceil(own_n / 32) words,
+ * bit = id - own_begin), and scans the shard with kge_topk's kernels on a
+ * shard-local view; the shard's parts are reduced with own_begin added.
+ *   queries [nq,3], mode, k: as kge_topk.  A fixed-side id or relation out of
+ *   range sets KGE_DEVERR_INDEX; that query's list is all padding, the others
+ *   proceed.  The predicted column is never read and never range-checked.
+ *   flags: the path's low bits (0 auto, 2 register tile, 3 wave scan), with
+ *   kge_topk's eligibility rules applied to the SHARD'S FIRST ROW (its
+ *   alignment decides, not the table's), | KGE_RANK_FILTER_TABLE.
+ *   filt_off / filt_ids: both forms of kge_topk; both NULL: no filter.  A
+ *   filter id inside [0, nentity) but outside the shard is not this shard's: no
+ *   bit, no error.  One outside [0, nentity) sets KGE_DEVERR_INDEX.
+ *   parts: as kge_topk, cutting THIS shard's rows.
+ *   own_begin == own_end is a valid empty shard: all-padding lists, no scan.
+ *   fixed_rows needs float alignment only.  Nothing allocates or synchronises;
+ *   the bitmap is zeroed by a kernel.  Both stages write every output place.
+ * Host checks, in this order: the model (as every entry); the mode (KGE_SINGLE:
+ * KGE_ERR_MODE); a NULL descriptor (KGE_ERR_ARG), then its struct_size
+ * (KGE_ERR_ABI); then KGE_ERR_ARG for a stage that is neither of the two,
+ * own_begin > own_end or a range outside [0, nentity], flags with other bits or
+ * a path that is not 0, 2 or 3, parts < 0, null queries / err_flag, a NULL
+ * buffer of the stage (LIST: fixed_rows, list_scores, list_ids; MERGE:
+ * lists_scores, lists_ids, ids_out, scores_out), filt_off without filt_ids,
+ * and nq < 0; nq == 0 returns KGE_OK; then KGE_ERR_DIM for k < 1 or
+ * k > KGE_TOPK_MAX_K, nq > 65535 (LIST), world outside 1..64 (MERGE) and rows
+ * over 2048 floats per (half-)row; the path's fit (LIST, path 2 for rows the
+ * tile cannot take: KGE_ERR_ARG); the workspace (KGE_ERR_WORKSPACE).
+ * LIST's workspace holds the q vectors, the shard's bitmap, pRotatE's phase
+ * tables over the own rows and the [nq, parts, k] partial lists: it grows with
+ * the shard, not with the table.  MERGE needs the 256-byte minimum.
+ * NOT pinned for this entry: graph capture, and tables past 2 GiB (row offsets
+ * are 64-bit, but no test runs it there).
+ */
+#define KGE_TSHARD_LIST  1
+#define KGE_TSHARD_MERGE 2
+typedef struct kge_topk_shard_desc {
+  int32_t struct_size;          /* = sizeof(kge_topk_shard_desc) (else KGE_ERR_ABI) */
+  int32_t flags;                /* path low bits (0 auto, 2 tile, 3 scan) | KGE_RANK_FILTER_TABLE */
+  int32_t k, parts;             /* as kge_topk; parts cuts THIS shard's rows */
+  int32_t world, reserved;      /* MERGE: lists to merge, 1..64 */
+  int64_t own_begin, own_end;   /* global ids; own_begin == own_end is a valid empty shard */
+  const float *fixed_rows;      /* [nq, entity_dim], reduced output of KGE_RSHARD_ROWS */
+  const int64_t *filt_off, *filt_ids; /* both forms of kge_topk; both NULL: no filter */
+  float *list_scores; int32_t *list_ids;               /* LIST out  [nq, k] */
+  const float *lists_scores; const int32_t *lists_ids; /* MERGE in  [world, nq, k], rank-major */
+  int64_t *ids_out; float *scores_out;                 /* MERGE out [nq, k] */
+} kge_topk_shard_desc;
+size_t kge_topk_shard_workspace_bytes(const kge_model_desc *m, const kge_topk_shard_desc *sh, int32_t stage,
+                                      int64_t nq);
+int kge_topk_shard(const kge_model_desc *m, int32_t mode, const kge_topk_shard_desc *sh, int32_t stage,
+                   const int64_t *queries, int64_t nq, void *workspace, size_t workspace_bytes,
+                   int32_t *err_flag, void *stream);
+
+/*
  * pRotatE ranks bit-exact to the reference — whose sin (model.py:245) is its
  * CPU vector library's (ATen → MKL VML here), which no device instruction
  * sequence reproduces — in three calls on one stream and workspace:

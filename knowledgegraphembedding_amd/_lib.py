@@ -25,6 +25,8 @@ RANK_LIST_CAP = 1024  # KGE_RANK_LIST_CAP
 PHASE_ROWS, PHASE_ENTITY, PHASE_FINALIZE, PHASE_ALL = 1, 2, 4, 7
 SHIP_Q, SHIP_ROWS, SHIP_MERGE, SHIP_CHAIN, SHIP_ENTITY = 1, 2, 3, 4, 5
 RSHARD_ROWS, RSHARD_TRUE, RSHARD_COUNT = 1, 2, 3  # KGE_RSHARD_*
+TSHARD_LIST, TSHARD_MERGE = 1, 2  # KGE_TSHARD_*
+TOPK_PAD_ID = 0x7FFFFFFF  # the id of an unused place of a KGE_TSHARD_LIST list (its score: -inf)
 ERR_HIP_BASE = 1000
 
 
@@ -108,6 +110,20 @@ class RankShardDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("own_begin", C.c_int64), ("own_end", C.c_int64),
                 ("fixed_rows", C.c_void_p), ("s_true", C.c_void_p), ("filt_off", C.c_void_p),
                 ("filt_ids", C.c_void_p), ("counts", C.c_void_p)]
+
+
+class TopkShardDesc(C.Structure):
+    """struct kge_topk_shard_desc (sharded top-k, kge_topk_shard; struct_size is set on construction)."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TopkShardDesc)
+
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("k", C.c_int32), ("parts", C.c_int32),
+                ("world", C.c_int32), ("reserved", C.c_int32), ("own_begin", C.c_int64), ("own_end", C.c_int64),
+                ("fixed_rows", C.c_void_p), ("filt_off", C.c_void_p), ("filt_ids", C.c_void_p),
+                ("list_scores", C.c_void_p), ("list_ids", C.c_void_p), ("lists_scores", C.c_void_p),
+                ("lists_ids", C.c_void_p), ("ids_out", C.c_void_p), ("scores_out", C.c_void_p)]
 
 
 _P = C.c_void_p
@@ -195,6 +211,8 @@ SIGNATURES = {
     "kge_rank_relations": (C.c_int, [_DESC, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_shard_workspace_bytes": (_SZ, [_DESC, _I64]),
     "kge_rank_shard": (C.c_int, [_DESC, _I32, C.POINTER(RankShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
+    "kge_topk_shard_workspace_bytes": (_SZ, [_DESC, C.POINTER(TopkShardDesc), _I32, _I64]),
+    "kge_topk_shard": (C.c_int, [_DESC, _I32, C.POINTER(TopkShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
     "kge_rank_sin_args": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_finish_sin": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_stage_timer": (C.c_int, [_I32, _P, _I32]),

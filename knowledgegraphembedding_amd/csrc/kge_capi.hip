@@ -1552,6 +1552,162 @@ int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
   return launch_status(launch_topk_merge(w.pscore, w.pid, w.state, nq, parts, k, ids_out, scores_out, s));
 }
 
+// ---- sharded top-k (kge_topk_shard)
+// LIST runs kge_topk's scan kernels on a shard-local view of the table: the
+// entity pointer at the shard's first row, nentity = the shard's rows, ids local
+// (ascending as the global ones, so the tie rule holds inside the shard); the
+// shard's merge adds own_begin.  Alignment, and with it the path's fit and the
+// 16-byte slots, is that of the shard's first row.
+kge_model_desc shard_view(const kge_model_desc* m, int64_t own_begin, int64_t own_end) {
+  kge_model_desc v = *m;
+  v.entity_embedding = m->entity_embedding + own_begin * (int64_t)m->entity_dim;
+  v.nentity = own_end - own_begin;
+  return v;
+}
+
+struct TopkShardWs {
+  float *q, *qph, *eph, *pscore;
+  int64_t* state;
+  uint32_t* bits;
+  int32_t* pid;
+};
+// v: the shard's view; rows = its row count (0: nothing but q and the states)
+TopkShardWs carve_topk_shard(void* ws, const kge_model_desc* v, int64_t rows, int64_t nq, int k, int parts,
+                             size_t* bytes) {
+  Carver c(ws);
+  TopkShardWs w;
+  const bool ph = rows > 0 && v->model == KGE_PROTATE && rank_path(v, RP_TILE) == RP_TILE;
+  w.eph = c.take<float>(ph ? 2 * rows * (int64_t)v->entity_dim : 0);
+  w.qph = c.take<float>(ph ? 2 * nq * (int64_t)v->entity_dim : 0);
+  w.q = c.take<float>(nq * (int64_t)v->entity_dim);
+  w.state = c.take<int64_t>(nq);
+  w.bits = c.take<uint32_t>(nq * ((rows + 31) / 32));
+  w.pscore = c.take<float>(nq * (int64_t)parts * k);
+  w.pid = c.take<int32_t>(nq * (int64_t)parts * k);
+  *bytes = c.off + 256;
+  return w;
+}
+
+// the shard's parts (topk_parts over its rows; an empty shard has none)
+int topk_shard_parts(const kge_model_desc* v, int64_t rows, int64_t nq, int32_t parts, int64_t* span) {
+  *span = 0;
+  return rows > 0 ? topk_parts(v, nq, parts, span) : 0;
+}
+
+int topk_shard_impl(const kge_model_desc* m, int32_t mode, const kge_topk_shard_desc* sh, int32_t stage,
+                    const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                    void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!sh) return KGE_ERR_ARG;
+  if (sh->struct_size != (int32_t)sizeof(kge_topk_shard_desc)) return KGE_ERR_ABI;
+  const bool list = stage == KGE_TSHARD_LIST;
+  if (!list && stage != KGE_TSHARD_MERGE) return KGE_ERR_ARG;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
+  if (sh->flags & ~(7 | KGE_RANK_FILTER_TABLE)) return KGE_ERR_ARG;
+  const int path = sh->flags & 7;
+  if (path != RP_AUTO && path != RP_TILE && path != RP_SCAN) return KGE_ERR_ARG;  // (no MFMA top-k)
+  if (sh->parts < 0) return KGE_ERR_ARG;
+  if (!queries || !err_flag) return KGE_ERR_ARG;
+  if (list && (!sh->fixed_rows || !sh->list_scores || !sh->list_ids)) return KGE_ERR_ARG;
+  if (!list && (!sh->lists_scores || !sh->lists_ids || !sh->ids_out || !sh->scores_out)) return KGE_ERR_ARG;
+  if (sh->filt_off && !sh->filt_ids) return KGE_ERR_ARG;
+  if (nq < 0) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  const int k = sh->k;
+  if (k < 1 || k > KGE_TOPK_MAX_K) return KGE_ERR_DIM;
+  if (list && nq > 65535) return KGE_ERR_DIM;  // kge_topk's ceiling, kept: the two take the same blocks of queries
+  if (!list && (sh->world < 1 || sh->world > 64)) return KGE_ERR_DIM;  // a lane of the merge wave per list
+  if (geo.ns == 0) return KGE_ERR_DIM;  // rows over 2048 floats: not served
+  hipStream_t s = as_stream(stream);
+  const int md = kernel_mode(mode);
+
+  if (!list) {
+    if (!workspace || workspace_bytes < 256) return KGE_ERR_WORKSPACE;
+    TopkShardMergeArgs g;
+    memset(&g, 0, sizeof(g));
+    g.ps = sh->lists_scores; g.pi = sh->lists_ids; g.nq = nq; g.stride_l = nq * (int64_t)k; g.stride_q = k;
+    g.nlists = sh->world; g.k = k; g.final = 1; g.queries = queries; g.head = mode == KGE_HEAD_BATCH ? 1 : 0;
+    g.E = m->nentity; g.R = m->nrelation; g.ids_out = sh->ids_out; g.scores_out = sh->scores_out;
+    return launch_status(launch_topk_merge_shard(g, s));
+  }
+
+  const int64_t rows = sh->own_end - sh->own_begin;
+  const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
+  const bool tile_ok = rank_path(&v, RP_TILE) == RP_TILE;
+  if (path == RP_TILE && !tile_ok) return KGE_ERR_ARG;
+  const bool tile = (path == RP_SCAN) ? false : tile_ok;
+  int64_t span = 0;
+  const int parts = topk_shard_parts(&v, rows, nq, sh->parts, &span);
+  size_t need = 0;
+  const TopkShardWs w = carve_topk_shard(workspace, &v, rows, nq, k, parts, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  const ModelOps& ops = ops_for(m->model);
+  const int K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  const int64_t W = (rows + 31) / 32;
+  // 1. q and each query's state, from fixed_rows (16-byte slots by ITS alignment and the relation table's)
+  kge_model_desc fv = *m;
+  fv.entity_embedding = sh->fixed_rows;
+  Geom fgeo;
+  st = check_model(&fv, &fgeo);
+  if (st) return st;
+  TopkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rel = m->relation_embedding; a.modulus = m->modulus; a.fixed_rows = sh->fixed_rows;
+  a.queries = queries; a.nq = nq; a.E = m->nentity; a.R = m->nrelation;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.eg = fgeo.eg; a.c = consts_of(m);
+  a.q = w.q; a.state = w.state; a.err = err_flag;
+  a.stage = 2;
+  st = launch_status(ops.topk(md, fgeo.vec, fgeo.ns, a, s));
+  if (st) return st;
+  // 2. the excluded rows of the shard as a bitmap
+  if (sh->filt_off)
+    st = launch_status(launch_filter_bits_range(queries, mode == KGE_HEAD_BATCH ? 1 : 0,
+                                                (sh->flags & KGE_RANK_FILTER_TABLE) ? 1 : 0, sh->filt_off,
+                                                sh->filt_ids, nq, m->nentity, m->nrelation, sh->own_begin,
+                                                sh->own_end, w.bits, err_flag, s));
+  else
+    st = launch_status(launch_zero(w.bits, nq * W, s));
+  if (st) return st;
+  // 3. the partial lists over the shard's view (an empty shard: none)
+  if (rows > 0) {
+    Geom vgeo;
+    st = check_model(&v, &vgeo);
+    if (st) return st;
+    if (tile) {
+      if (m->model == KGE_PROTATE) {
+        st = launch_status(launch_prot_phase(v.entity_embedding, rows, K, a.c.kappa_p, 1, w.eph, s));
+        if (!st) st = launch_status(launch_prot_phase(w.q, nq, K, 0.f, 0, w.qph, s));
+        if (st) return st;
+      }
+      TopkTileArgs b;
+      memset(&b, 0, sizeof(b));
+      b.t.q = w.q; b.t.ent = v.entity_embedding; b.t.modulus = m->modulus;
+      b.t.nq = nq; b.t.E = rows; b.t.Le = m->entity_dim; b.t.K = K;
+      b.t.c = a.c; b.t.true_id = w.state; b.t.fbits = w.bits; b.t.W = W;
+      b.t.qph = w.qph; b.t.eph = w.eph;
+      b.k = k; b.parts = parts; b.span = span; b.pscore = w.pscore; b.pid = w.pid;
+      st = launch_status(ops.topk_tile(md, b, s));
+    } else {
+      a.ent = v.entity_embedding; a.E = rows; a.eg = vgeo.eg; a.fbits = w.bits; a.W = W;
+      a.k = k; a.parts = parts; a.span = span; a.pscore = w.pscore; a.pid = w.pid;
+      a.stage = 1;
+      st = launch_status(ops.topk(md, vgeo.vec, vgeo.ns, a, s));
+    }
+    if (st) return st;
+  }
+  // 4. the shard's list, global ids
+  TopkShardMergeArgs g;
+  memset(&g, 0, sizeof(g));
+  g.ps = w.pscore; g.pi = w.pid; g.nq = nq; g.stride_l = k; g.stride_q = (int64_t)parts * k;
+  g.nlists = parts; g.k = k; g.final = 0; g.id_base = (int32_t)sh->own_begin;
+  g.ls = sh->list_scores; g.li = sh->list_ids;
+  return launch_status(launch_topk_merge_shard(g, s));
+}
+
 // ---- ranking against candidate lists (kge_rank_candidates)
 // The chunks of a query's list: one when the queries alone fill the device
 // (256 CUs × 8 workgroups), else enough to, of at least 64 candidates each and
@@ -2320,6 +2476,30 @@ int kge_rank_shard(const kge_model_desc* m, int32_t mode, const kge_rank_shard_d
                    const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
                    void* stream) {
   return rank_shard_impl(m, mode, sh, stage, queries, nq, workspace, workspace_bytes, err_flag, stream);
+}
+
+// 0: a bad model, descriptor, stage, range, k or nq (the call itself says which)
+size_t kge_topk_shard_workspace_bytes(const kge_model_desc* m, const kge_topk_shard_desc* sh, int32_t stage,
+                                      int64_t nq) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0) return 0;
+  if (!sh || sh->struct_size != (int32_t)sizeof(kge_topk_shard_desc)) return 0;
+  if (stage == KGE_TSHARD_MERGE) return 256;
+  if (stage != KGE_TSHARD_LIST) return 0;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return 0;
+  if (sh->k < 1 || sh->k > KGE_TOPK_MAX_K || sh->parts < 0) return 0;
+  const int64_t rows = sh->own_end - sh->own_begin;
+  const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
+  int64_t span = 0;
+  size_t b = 0;
+  carve_topk_shard(nullptr, &v, rows, nq, sh->k, topk_shard_parts(&v, rows, nq, sh->parts, &span), &b);
+  return b;
+}
+
+int kge_topk_shard(const kge_model_desc* m, int32_t mode, const kge_topk_shard_desc* sh, int32_t stage,
+                   const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                   void* stream) {
+  return topk_shard_impl(m, mode, sh, stage, queries, nq, workspace, workspace_bytes, err_flag, stream);
 }
 
 int kge_rank_sin_args(const kge_model_desc* m, int32_t mode, int64_t nq, const int64_t* item_off, float* args_out,

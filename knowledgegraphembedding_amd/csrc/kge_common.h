@@ -80,6 +80,33 @@ int launch_rel_trig_table(const float* rel, int64_t R, int Lr, float kappa, floa
 // kge_topk's reduction of every query's `parts` partial lists (kge_common.hip)
 int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
                       int64_t* ids_out, float* scores_out, hipStream_t s);
+// kge_topk_shard's two reductions (kge_common.hip, k_topk_merge_shard): list l of query q lies at
+// l * stride_l + q * stride_q.  Final = 0 (a shard's parts → its list): ids + id_base, padding kept
+// as (−∞, INT32_MAX), into ls / li.  Final = 1 (the ranks' lists → the result): padding → (−1, −∞),
+// a query whose fixed-side id or relation is out of range → (−1, NaN), into ids_out / scores_out.
+struct TopkShardMergeArgs {
+  const float* ps;
+  const int32_t* pi;
+  int64_t nq, stride_l, stride_q;
+  int nlists, k;            // nlists 0..64 (0: every place is padding)
+  int final;
+  int32_t id_base;
+  const int64_t* queries;   // final: [nq, 3]
+  int head;                 // final: head-batch (the fixed side is t)
+  int64_t E, R;
+  float* ls;
+  int32_t* li;
+  int64_t* ids_out;
+  float* scores_out;
+};
+int launch_topk_merge_shard(const TopkShardMergeArgs& a, hipStream_t s);
+// kge_topk_shard's exclusion bitmap over the rows [lo, hi) only (kge_rank_mfma.hip): bits [nq, W],
+// W = ceil((hi − lo) / 32), bit = id − lo.  tab != 0: off / ids are the whole filter index, looked up
+// by the query's key (head picks it); else per-query lists.  Ids of [0, E) outside the range set no
+// bit; ids outside [0, E) set KGE_DEVERR_INDEX.
+int launch_filter_bits_range(const int64_t* queries, int head, int tab, const int64_t* off, const int64_t* ids,
+                             int64_t nq, int64_t E, int64_t R, int64_t lo, int64_t hi, uint32_t* bits, int32_t* err,
+                             hipStream_t s);
 // `words` 32-bit words at p set to zero by a kernel of this library (kge_common.hip).  Not
 // hipMemsetAsync: captured into a graph, its memset node filled the counters with a stale 16-byte
 // pattern on a later replay (tests/test_graph_gpu.py), where a kernel node replays its arguments.

@@ -382,7 +382,67 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ ps
     }
   }
 }
+
+// kge_topk_shard's merges: k_topk_merge's butterfly over lists addressed by
+// two strides (a shard's parts are query-major, the ranks' gathered lists
+// rank-major).  Ids are distinct across lists (disjoint candidate ranges), and
+// every list is full: its unused places hold (−∞, TOPK_NO_ID).
+__global__ __launch_bounds__(256) void k_topk_merge_shard(TopkShardMergeArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= a.nq) return;
+  const int k = a.k;
+  if (a.final) {
+    const int64_t x = a.queries[q * 3 + (a.head ? 2 : 0)], r = a.queries[q * 3 + 1];
+    if (x < 0 || x >= a.E || r < 0 || r >= a.R) {  // (wave-uniform)
+      for (int p = lane; p < k; p += 64) {
+        a.ids_out[q * k + p] = -1;
+        a.scores_out[q * k + p] = __builtin_nanf("");
+      }
+      return;
+    }
+  }
+  const bool has = lane < a.nlists;
+  const int64_t base = (has ? lane : 0) * a.stride_l + q * a.stride_q;
+  int head = 0;
+  float hs = has ? a.ps[base] : -__builtin_inff();
+  int32_t hi = has ? a.pi[base] : TOPK_NO_ID;
+  for (int o = 0; o < k; ++o) {
+    float bs = hs;
+    int32_t bi = hi;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+      const float os = __shfl_xor(bs, d);
+      const int32_t oi = __shfl_xor(bi, d);
+      if (os > bs || (os == bs && oi < bi)) {
+        bs = os;
+        bi = oi;
+      }
+    }
+    const bool pad = bi == TOPK_NO_ID;
+    if (lane == 0) {
+      if (a.final) {
+        a.ids_out[q * k + o] = pad ? -1 : (int64_t)bi;
+        a.scores_out[q * k + o] = pad ? -__builtin_inff() : bs;
+      } else {
+        a.li[q * k + o] = pad ? TOPK_NO_ID : bi + a.id_base;
+        a.ls[q * k + o] = pad ? -__builtin_inff() : bs;
+      }
+    }
+    if (has && hi == bi && !pad) {
+      ++head;
+      hs = (head < k) ? a.ps[base + head] : -__builtin_inff();
+      hi = (head < k) ? a.pi[base + head] : TOPK_NO_ID;
+    }
+  }
+}
 }  // namespace
+
+int launch_topk_merge_shard(const TopkShardMergeArgs& a, hipStream_t s) {
+  if (a.nlists < 0 || a.nlists > 64 || a.k < 1) return -1;
+  hipLaunchKernelGGL(k_topk_merge_shard, dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
 
 int launch_topk_merge(const float* pscore, const int32_t* pid, const int64_t* state, int64_t nq, int parts, int k,
                       int64_t* ids_out, float* scores_out, hipStream_t s) {

@@ -310,7 +310,8 @@ struct TileArgs {
 // list of its k best unexcluded candidates sorted by (score descending, id
 // ascending) and writes it to pscore / pid [nq, parts, k] (unused places:
 // score −∞, id INT32_MAX); k_topk_merge reduces a query's lists.
-// k_topk_prep / k_topk_scan (stage 0 / 1):
+// k_topk_prep / k_topk_scan (stage 0 / 1); k_topk_prep_rows (stage 2,
+// kge_topk_shard): q from the caller's fixed_rows, no table read:
 struct TopkArgs {
   const float* ent;
   const float* rel;
@@ -331,6 +332,7 @@ struct TopkArgs {
   int32_t* pid;
   int32_t* err;
   int stage;
+  const float* fixed_rows;  // [nq, Le] stage 2: the fixed side's rows (E, R: the global counts)
 };
 // (both negative: the bitmap launches read state as "true id", and set no bit for it)
 constexpr int64_t TOPK_VALID = -1, TOPK_BAD = -2;

@@ -15,6 +15,8 @@
 //                  reference's own fp32 operation order (kge_rank_ref.h)
 //   k_topk_prep / k_topk_tile / k_topk_scan   top-k link prediction (kge_topk): the
 //                  ranking's all-entity passes with a selecting epilogue
+//   k_topk_prep_rows   kge_topk_shard's prep: q from the caller's fixed_rows; the two
+//                  scan kernels then run unchanged on a shard-local view of the table
 #include "kge_internal.h"
 #include "kge_rank_ref.h"
 #include "kge_rel.h"
@@ -1856,6 +1858,33 @@ __global__ __launch_bounds__(256) void k_topk_prep(TopkArgs a) {
   if (bad) return;
   R_ q, xr, rr;
   load_row<NS, VEC, CPLX>(a.ent + x * a.Le, a.eg, lane, xr);
+  load_rel<M, NS, VEC, CPLX>(a.rel + r * a.Lr, a.eg, lane, rr);
+  build_q<M, MODE, NS, VEC, CPLX>(xr, rr, c, q);
+  store_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
+}
+
+// kge_topk_shard's prep: k_topk_prep with the fixed side's row taken from
+// fixed_rows[qi] (KGE_RSHARD_ROWS, reduced) and not from a table — the same
+// load_row / build_q on the same bits, so the same q.  a.E is the global
+// entity count; qsan is not written (the ranged bitmap reads the queries).
+template <int M, int MODE, int VEC, int NS>
+__global__ __launch_bounds__(256) void k_topk_prep_rows(TopkArgs a) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  using R_ = Row<NS, VEC, CPLX>;
+  const int lane = threadIdx.x & 63;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + wave_id();
+  if (qi >= a.nq) return;
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int64_t x = a.queries[qi * 3 + (MODE == HEAD_BATCH ? 2 : 0)], r = a.queries[qi * 3 + 1];
+  const bool bad = x < 0 || x >= a.E || r < 0 || r >= a.R;
+  if (lane == 0) {
+    a.state[qi] = bad ? TOPK_BAD : TOPK_VALID;
+    if (bad) atomicOr(a.err, KGE_DEVERR_INDEX);
+  }
+  if (bad) return;
+  R_ q, xr, rr;
+  load_row<NS, VEC, CPLX>(a.fixed_rows + qi * a.Le, a.eg, lane, xr);
   load_rel<M, NS, VEC, CPLX>(a.rel + r * a.Lr, a.eg, lane, rr);
   build_q<M, MODE, NS, VEC, CPLX>(xr, rr, c, q);
   store_row<NS, VEC, CPLX>(a.q + qi * a.Le, a.eg, lane, q);
@@ -3703,6 +3732,8 @@ struct RunTopk {
     } else {
       if (a.stage == 0) {
         hipLaunchKernelGGL((k_topk_prep<M, MODE, VEC, NS>), dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, s, a);
+      } else if (a.stage == 2) {
+        hipLaunchKernelGGL((k_topk_prep_rows<M, MODE, VEC, NS>), dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, s, a);
       } else {
         const int64_t units = a.nq * a.parts;
         hipLaunchKernelGGL((k_topk_scan<M, MODE, VEC, NS>), dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, a);

@@ -365,6 +365,56 @@ __global__ __launch_bounds__(256) void k_filter_bits_lds(const int64_t* __restri
 // rows up to this many words go through k_filter_bits_lds (E ≤ 393,216)
 constexpr int FB_LDS_WORDS = 12288;
 
+// kge_topk_shard's bitmap over the rows [lo, hi) only, one block per query:
+// bit = id − lo; an id of [0, E) outside the range is another shard's and sets
+// nothing, one outside [0, E) sets KGE_DEVERR_INDEX.  There is no true id.
+// LDS: the row is built in LDS and written whole (k_filter_bits_lds's scheme);
+// else the caller has zeroed `bits` and the atomics go to global memory.  `tab`:
+// the whole filter index, the query's key from its fixed side and relation (the
+// predicted column is not read); a query whose key is out of range sets no bit
+// (the prep kernel flags it).
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_filter_bits_range(const int64_t* __restrict__ queries, int head, int tab,
+                                                           const int64_t* __restrict__ off,
+                                                           const int64_t* __restrict__ ids, int64_t E, int64_t R,
+                                                           int64_t lo, int64_t hi, int64_t W,
+                                                           uint32_t* __restrict__ bits, int32_t* err) {
+  extern __shared__ uint32_t fbr_row[];
+  const int64_t q = blockIdx.x;
+  const int tid = threadIdx.x;
+  uint32_t* row = LDS ? fbr_row : bits + q * W;
+  if constexpr (LDS) {
+    for (int64_t k = tid; k < W; k += 256) fbr_row[k] = 0u;
+    __syncthreads();
+  }
+  int64_t b = 0, e_ = 0;
+  if (tab) {
+    const int64_t x = queries[q * 3 + (head ? 2 : 0)], r = queries[q * 3 + 1];
+    if (x >= 0 && x < E && r >= 0 && r < R) {
+      const int64_t key = head ? r * E + x : x * R + r;
+      b = off[key];
+      e_ = off[key + 1];
+    }
+  } else {
+    b = off[q];
+    e_ = off[q + 1];
+  }
+  for (int64_t p = b + tid; p < e_; p += 256) {
+    const int64_t e = ids[p];
+    if (e < 0 || e >= E) {
+      atomicOr(err, KGE_DEVERR_INDEX);
+      continue;
+    }
+    if (e < lo || e >= hi) continue;
+    atomicOr(&row[(e - lo) >> 5], 1u << ((e - lo) & 31));
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    uint32_t* dst = bits + q * W;
+    for (int64_t k = tid; k < W; k += 256) dst[k] = fbr_row[k];
+  }
+}
+
 // rank = 1 + #{strictly greater} (counted beyond the window + refined inside
 // it), or the exact rescan's count for an overflowed window
 __global__ __launch_bounds__(256) void k_rank_emit(EmitArgs a) {
@@ -906,6 +956,23 @@ int launch_filter_bits_tab(const int64_t* queries, int head, const int64_t* tab,
   if (int z = launch_zero(bits, nq * W, s)) return z;
   hipLaunchKernelGGL(k_filter_bits_tab, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, queries, head, tab, vals,
                      true_id, nq, E, R, W, bits, err);
+  return (int)hipGetLastError();
+}
+
+int launch_filter_bits_range(const int64_t* queries, int head, int tab, const int64_t* off, const int64_t* ids,
+                             int64_t nq, int64_t E, int64_t R, int64_t lo, int64_t hi, uint32_t* bits, int32_t* err,
+                             hipStream_t s) {
+  const int64_t W = (hi - lo + 31) / 32;
+  if (nq > 0x7fffffff || lo < 0 || hi < lo || hi > E) return -1;
+  if (nq == 0) return 0;
+  if (W <= FB_LDS_WORDS) {  // (an empty range too: no word is written, the ids are still checked)
+    hipLaunchKernelGGL(k_filter_bits_range<true>, dim3((unsigned)nq), dim3(256), (size_t)W * 4, s, queries, head, tab,
+                       off, ids, E, R, lo, hi, W, bits, err);
+    return (int)hipGetLastError();
+  }
+  if (int z = launch_zero(bits, nq * W, s)) return z;
+  hipLaunchKernelGGL(k_filter_bits_range<false>, dim3((unsigned)nq), dim3(256), 0, s, queries, head, tab, off, ids, E,
+                     R, lo, hi, W, bits, err);
   return (int)hipGetLastError();
 }
 

@@ -809,6 +809,102 @@ def topk(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, k: int, dev, fi
     return out_ids, out_s
 
 
+def _topk_shard_args(name: str, desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, k: int, dev):
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("mode %s not supported" % mode)
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k = {k}: expected 1 .. {TOPK_MAX_K}")
+    q = _idx(queries, dev)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"queries: {tuple(q.shape)}, expected [nq, 3]")
+
+    def buf(t, what, numel, dtype):
+        if (t is None or t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of {numel} elements on {dev}")
+        return t.data_ptr()
+
+    return q, int(k), buf
+
+
+def topk_shard_list(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, k: int, dev,
+                    fixed_rows: torch.Tensor, filt=None, filter_table: bool = False, path: str = "auto",
+                    parts: int = 0, *, out=None, workspace: Optional[torch.Tensor] = None):
+    """Stage LIST of the sharded top-k (kge_topk_shard): `desc` addresses the
+    shard by GLOBAL row id, as rank_shard_rows takes it; `fixed_rows`
+    [nq, entity_dim] is the all-reduced output of rank_shard_rows.  Returns
+    (scores float32 [nq, k], ids int32 [nq, k]): the k best unexcluded rows of
+    own = (begin, end) per query, ordered by (score descending, id ascending),
+    GLOBAL ids; unused places hold (-inf, TOPK_PAD_ID = INT32_MAX), which lose
+    to every candidate when the ranks' lists are merged.  `filt`,
+    `filter_table`, `path`, `parts` as topk (the path's fit is judged on the
+    shard's first row; parts cuts this shard's rows).  At most 65535 queries.
+    `out` = (scores, ids) and `workspace`: the caller's buffers.  The device
+    error flag is left for the caller's next read."""
+    if path not in TOPK_PATHS:
+        raise ValueError("top-k path %s not supported" % path)
+    q, k, buf = _topk_shard_args("topk_shard_list", desc, mode, queries, k, dev)
+    nq = q.shape[0]
+    b, e = int(own[0]), int(own[1])
+    if not 0 <= b <= e <= desc.nentity:
+        raise ValueError(f"own range [{b}, {e}) is not inside [0, {desc.nentity}]")
+    if out is None:
+        out = (torch.empty(nq, k, dtype=torch.float32, device=dev), torch.empty(nq, k, dtype=torch.int32, device=dev))
+    sh = _lib.TopkShardDesc()
+    sh.own_begin, sh.own_end, sh.k, sh.parts = b, e, k, int(parts)
+    sh.flags = TOPK_PATHS[path] | (_lib.RANK_FILTER_TABLE if filter_table else 0)
+    sh.fixed_rows = buf(fixed_rows, "fixed_rows", nq * desc.entity_dim, torch.float32)
+    sh.list_scores = buf(out[0], "scores", nq * k, torch.float32)
+    sh.list_ids = buf(out[1], "ids", nq * k, torch.int32)
+    keep = None
+    if filt is not None:
+        _check_filter_shape(desc, nq, filt[0], filter_table)
+        off = _idx(filt[0], dev)
+        ids = _idx(filt[1], dev) if filt[1].numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+        keep = (off, ids)
+        sh.filt_off, sh.filt_ids = off.data_ptr(), ids.data_ptr()
+    lib = _lib.load()
+    st = state(dev)
+    ws = workspace if workspace is not None else st.workspace(
+        lib.kge_topk_shard_workspace_bytes(desc, sh, _lib.TSHARD_LIST, nq))
+    _lib.check(lib.kge_topk_shard(desc, _lib.MODE_IDS[mode], sh, _lib.TSHARD_LIST, q.data_ptr(), nq, ws.data_ptr(),
+                                  ws.numel(), st.err.data_ptr(), _stream(dev)), "kge_topk_shard")
+    del keep  # (the launches are queued on the stream the caching allocator frees behind)
+    return out
+
+
+def topk_shard_merge(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, k: int, dev,
+                     lists_scores: torch.Tensor, lists_ids: torch.Tensor, *, out=None,
+                     workspace: Optional[torch.Tensor] = None):
+    """Stage MERGE of the sharded top-k: `lists_scores` / `lists_ids`
+    [world, nq, k] are the ranks' topk_shard_list outputs, all-gathered
+    rank-major (world <= 64).  Returns (ids int64 [nq, k], scores float32
+    [nq, k]) as topk does: padded with (-1, -inf); a query whose fixed-side id
+    or relation is out of range gets (-1, NaN) on every rank.  Only desc's
+    nentity / nrelation are used: no table row is read.  The device error flag
+    is left for the caller's next read (raise_on_device_error)."""
+    q, k, buf = _topk_shard_args("topk_shard_merge", desc, mode, queries, k, dev)
+    nq = q.shape[0]
+    if lists_scores.dim() != 3 or not 1 <= lists_scores.shape[0] <= 64:
+        raise ValueError(f"lists_scores: {tuple(lists_scores.shape)}, expected [world <= 64, nq, k]")
+    world = lists_scores.shape[0]
+    if out is None:
+        out = (torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, dtype=torch.float32, device=dev))
+    sh = _lib.TopkShardDesc()
+    sh.k, sh.world = k, world
+    sh.own_begin, sh.own_end = 0, desc.nentity
+    sh.lists_scores = buf(lists_scores, "lists_scores", world * nq * k, torch.float32)
+    sh.lists_ids = buf(lists_ids, "lists_ids", world * nq * k, torch.int32)
+    sh.ids_out = buf(out[0], "ids", nq * k, torch.int64)
+    sh.scores_out = buf(out[1], "scores", nq * k, torch.float32)
+    lib = _lib.load()
+    st = state(dev)
+    ws = workspace if workspace is not None else st.workspace(
+        lib.kge_topk_shard_workspace_bytes(desc, sh, _lib.TSHARD_MERGE, nq))
+    _lib.check(lib.kge_topk_shard(desc, _lib.MODE_IDS[mode], sh, _lib.TSHARD_MERGE, q.data_ptr(), nq, ws.data_ptr(),
+                                  ws.numel(), st.err.data_ptr(), _stream(dev)), "kge_topk_shard")
+    return out
+
+
 def reference_sin(args: torch.Tensor) -> torch.Tensor:
     """sin of pRotatE phase sums as the reference evaluates them: its own
     `torch.sin` on the CPU (model.py:245; ATen's vectorized CPU kernel — MKL

@@ -447,6 +447,69 @@ class EntityRowPartition:
             ops.raise_on_device_error(dev)
         return r, t
 
+    def predict(self, model, queries, mode, k=10, all_true_triples=None, path="auto"):
+        """Top-k link prediction as KGEModel.predict — the same arguments, the
+        same (ids [nq, k] int64, scores [nq, k] float32) numpy pair, ids and
+        score bits — with the table used IN PLACE: every rank scans only its
+        own rows (kge_topk_shard) and ``materialize()`` is not called.
+        Collective: every rank passes the same queries and gets the same
+        result.  Per block of RANK_BLOCK queries: one int32 all-reduce of the
+        fixed side's rows (as rank_queries), each rank's k-list of its shard,
+        one all-gather of the lists (scores and ids packed in one 4-byte
+        buffer), and the merge of the world's lists on every rank.  The order (score descending, id
+        ascending) is total and a pair's score does not depend on which rows
+        share its scan, so the merged lists are the one-table result.
+        `path`: resolved by the library from the row shape and the alignment of
+        the shard's first row — the same on every rank for this partition's own
+        allocations (rows of a multiple of 16 bytes, or every shard start
+        equally aligned); a forced "tile" that one rank's shard cannot take
+        raises there."""
+        import numpy as np
+        from . import ops
+        from .filters import FilterIndex
+        if mode not in ('head-batch', 'tail-batch'):
+            raise ValueError('mode %s not supported' % mode)
+        if not 1 <= int(k) <= ops.TOPK_MAX_K:
+            raise ValueError('k = %s: expected 1 .. %d' % (k, ops.TOPK_MAX_K))
+        if self.world > 64:
+            raise ValueError('sharded top-k merges at most 64 ranks\' lists, not %d' % self.world)
+        k = int(k)
+        dev = self.shard.device
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int64).reshape(-1, 3)).copy()
+        q[:, 0 if mode == 'head-batch' else 2] = -1  # no "true" answer: only the known ones are excluded
+        index = table = None
+        if all_true_triples is not None:
+            index = all_true_triples if isinstance(all_true_triples, FilterIndex) else \
+                FilterIndex(all_true_triples, self.nentity, model.nrelation, device=dev)
+            if os.environ.get("KGE_RANK_FILTER_TABLE", "1") != "0":
+                table = index.device_table(mode, dev)
+        desc, own = self._own_desc(model)
+        ids_out, sc_out = [], []
+        with torch.no_grad():
+            for b0 in range(0, len(q), self.RANK_BLOCK):
+                qb = q[b0:b0 + self.RANK_BLOCK]
+                nq = len(qb)
+                qd = torch.from_numpy(np.ascontiguousarray(qb)).to(dev)
+                filt = table
+                if index is not None and table is None:
+                    filt = tuple(torch.from_numpy(x) for x in index.filter_csr(qb, mode))
+                fixed = torch.empty(nq, self.dim, device=dev)
+                ops.rank_shard_rows(desc, mode, qd, own, dev, fixed)
+                dist.all_reduce(fixed.view(torch.int32), op=dist.ReduceOp.SUM, group=self.group)
+                mine = torch.empty(2, nq, k, dtype=torch.float32, device=dev)  # scores | ids, 4 bytes each
+                ops.topk_shard_list(desc, mode, qd, own, k, dev, fixed, filt=filt, filter_table=table is not None,
+                                    path=path, out=(mine[0], mine[1].view(torch.int32)))
+                every = torch.empty(self.world, 2, nq, k, dtype=torch.float32, device=dev)
+                dist.all_gather_into_tensor(every.view(-1), mine.view(-1), group=self.group)
+                ids, scores = ops.topk_shard_merge(desc, mode, qd, k, dev, every[:, 0].contiguous(),
+                                                   every[:, 1].contiguous().view(torch.int32))
+                ids_out.append(ids)
+                sc_out.append(scores)
+            res = (torch.cat(ids_out).cpu().numpy() if ids_out else np.zeros((0, k), np.int64),
+                   torch.cat(sc_out).cpu().numpy() if sc_out else np.zeros((0, k), np.float32))
+            ops.raise_on_device_error(dev)
+        return res
+
     def test_step(self, model, test_triples, all_true_triples, args):
         """KGEModel.test_step's filtered metrics (model.py:315-429: head-batch
         queries, then tail-batch) from rank_queries — collective, the same
