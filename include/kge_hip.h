@@ -921,6 +921,78 @@ int kge_rank_shard(const kge_model_desc *m, int32_t mode, const kge_rank_shard_d
                    int32_t *err_flag, void *stream);
 
 /*
+ * SHARDED FILTERED RANKING, THE FAST COUNTING PASS — a drop-in for the call
+ * kge_rank_shard(..., KGE_RSHARD_COUNT, ...): the same descriptor and
+ * conventions (the entity pointer own_begin rows before the shard, nentity the
+ * global count, only rows [own_begin, own_end) read, fixed_rows and s_true the
+ * reduced outputs of the ROWS and TRUE stages), and sh->counts [2, nq] bit for
+ * bit what KGE_RSHARD_COUNT writes for the same arguments — a query with an id
+ * out of range (0 / 0 and KGE_DEVERR_INDEX), an empty shard, filter ids outside
+ * the shard or the table (no error), lists that repeat ids or list the true id,
+ * both filter forms, a true id owned by another rank.  A rank is an integer
+ * count: the fast pass of kge_rank_filtered_ex runs on a shard-local view (rows
+ * = own_end - own_begin, local id = global id - own_begin), counts every owned
+ * candidate whose fast score clears the query's near-tie window around s_true,
+ * and scores the others in the reference's order against the given s_true[q].
+ * s_true is already the reference-order score, so the window has to cover the
+ * candidate's own fast-pass error only; it uses the SHARD's table statistics.
+ * The true row is never read (its owner may be another rank); neither is the
+ * table row of the fixed side: q comes from fixed_rows[q] and the relation row
+ * (RotatE: m->relation_trig as in the other ranking entries).
+ *   listed_out [nq] int32, nullable: the owned candidates of query q that were
+ *   scored in the reference's order; 0 on path 3; above KGE_RANK_LIST_CAP the
+ *   query was rescanned exactly over the own rows (so is a query whose s_true
+ *   is infinite: no window catches a score of the same infinity).  The table's
+ *   rows are assumed finite, as by kge_rank_filtered_ex's fast paths: a fast
+ *   score that is NaN where the reference's is infinite is not listed.
+ *   sh->flags = path | optional KGE_RANK_FILTER_TABLE.  Paths:
+ *     0  auto: 1 where it fits, else 2 where it fits, else 3.
+ *     1  split-bf16 MFMA tile: DistMult and ComplEx, the shard's first row
+ *        16-byte aligned, the split operands within 32-bit buffer offsets.
+ *     2  register tile: TransE, DistMult, ComplEx and RotatE with reduction
+ *        length % 4 == 0 and the shard's first row 16-byte aligned (the
+ *        shard's alignment decides, not the table's, as in kge_topk_shard).
+ *     3  exact: KGE_RSHARD_COUNT's own kernel, for every shape that stage
+ *        serves.
+ *   An explicit path the shard's rows do not admit is KGE_ERR_ARG; so is path 4
+ *   (the fp32 MFMA tile is not offered here) and any path above 4.  pRotatE
+ *   resolves to path 3 — its window rests on the score-interval argument of the
+ *   one-table pipeline, which has no given-s_true form yet — and an explicit 1 or
+ *   2 for pRotatE is KGE_ERR_ARG.  Rows over 2048 floats per (half-)row, and a
+ *   RotatE relation_trig that is not 16-byte aligned while fixed_rows and the
+ *   relation table are, resolve to 3 likewise.
+ *   kge_rank_shard_fast_path: the path a call with these arguments takes (1, 2
+ *   or 3), or minus the status it is refused with.  fixed_rows must be set: its
+ *   alignment picks the q kernel's slots.
+ *   The call runs on the caller's stream only, allocates and synchronises
+ *   nothing, and every buffer it reads is initialised by a kernel.  The shard's
+ *   statistics and split operands are recomputed every call
+ *   (KGE_RANK_REUSE_TABLE is not offered).  Deterministic: the counts are
+ *   integers, whatever order the list was filled in.
+ * Host checks, in this order: the model; the mode; a NULL descriptor
+ * (KGE_ERR_ARG), then its struct_size (KGE_ERR_ABI); then KGE_ERR_ARG for
+ * own_begin > own_end or a range outside [0, nentity], flags with bits other
+ * than 7 | KGE_RANK_FILTER_TABLE or a path above 4, null queries / err_flag or
+ * nq < 0, and a NULL fixed_rows, s_true, counts, filt_off or filt_ids;
+ * nq == 0 returns KGE_OK; a resolved path 3 continues with KGE_RSHARD_COUNT's
+ * checks (its grid rule, its workspace); nq > 65535 on a resolved path 1 or 2
+ * (KGE_ERR_DIM: the bitmap and tile launches put queries on grid.y); the path's
+ * fit (KGE_ERR_ARG); the workspace (KGE_ERR_WORKSPACE).
+ * The workspace (kge_rank_shard_fast_workspace_bytes; 0 for arguments the call
+ * refuses) holds the fast and reference q vectors, the counters,
+ * nq x KGE_RANK_LIST_CAP list entries, the shard's bitmap [nq, ceil(rows/32)],
+ * the statistics and, on path 1, the split operands of the own rows and of q.
+ * It grows with the shard, never with the table, and holds no [nq, rows] score
+ * matrix; on path 3 it is kge_rank_shard_workspace_bytes.
+ * NOT pinned for this entry: graph capture, and tables past 2 GiB.
+ */
+size_t kge_rank_shard_fast_workspace_bytes(const kge_model_desc *m, const kge_rank_shard_desc *sh, int64_t nq);
+int kge_rank_shard_fast_path(const kge_model_desc *m, const kge_rank_shard_desc *sh);
+int kge_rank_shard_fast(const kge_model_desc *m, int32_t mode, const kge_rank_shard_desc *sh,
+                        const int64_t *queries, int64_t nq, int32_t *listed_out,
+                        void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/*
  * SHARDED TOP-K LINK PREDICTION — kge_topk over an entity table that is split
  * into row shards, one per rank, predicted in place: no rank ever holds
  * another's rows.  The conventions are kge_rank_shard's: m->entity_embedding

@@ -211,6 +211,9 @@ SIGNATURES = {
     "kge_rank_relations": (C.c_int, [_DESC, _P, _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "kge_rank_shard_workspace_bytes": (_SZ, [_DESC, _I64]),
     "kge_rank_shard": (C.c_int, [_DESC, _I32, C.POINTER(RankShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
+    "kge_rank_shard_fast_workspace_bytes": (_SZ, [_DESC, C.POINTER(RankShardDesc), _I64]),
+    "kge_rank_shard_fast_path": (C.c_int, [_DESC, C.POINTER(RankShardDesc)]),
+    "kge_rank_shard_fast": (C.c_int, [_DESC, _I32, C.POINTER(RankShardDesc), _P, _I64, _P, _P, _SZ, _P, _P]),
     "kge_topk_shard_workspace_bytes": (_SZ, [_DESC, C.POINTER(TopkShardDesc), _I32, _I64]),
     "kge_topk_shard": (C.c_int, [_DESC, _I32, C.POINTER(TopkShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
     "kge_rank_sin_args": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),

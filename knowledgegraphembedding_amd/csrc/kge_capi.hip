@@ -1941,6 +1941,164 @@ int rank_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_
   return launch_status(ops_for(m->model).rank_shard(kernel_mode(mode), stage, a, s));
 }
 
+// ---- sharded filtered ranking, the fast counting pass (kge_rank_shard_fast)
+// KGE_RSHARD_COUNT's counts from the single-table pipeline's fast pass on the
+// shard's view (shard_view, as kge_topk_shard): rank_path's rules applied to
+// the shard's first row.  pRotatE, rows the register prep kernel does not hold
+// and a trig table its 16-byte slots cannot read resolve to the exact stage.
+// fgeo: the prep kernel's slots (fixed_rows' alignment and the relation table's).
+int shard_fast_path(const kge_model_desc* m, const kge_rank_shard_desc* sh, int requested, Geom* fgeo) {
+  if (requested == RP_SCAN) return RP_SCAN;
+  if (requested < RP_AUTO || requested > RP_TILE) return -1;  // (the fp32 MFMA tile is not offered)
+  const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
+  kge_model_desc fv = *m;
+  fv.entity_embedding = sh->fixed_rows;
+  Geom g;
+  bool fast = m->model != KGE_PROTATE && check_model(&fv, &g) == KGE_OK && g.ns != 0;
+  if (fast && m->model == KGE_ROTATE && m->relation_trig && g.vec == 4 && !aligned16(m->relation_trig)) fast = false;
+  if (fgeo) *fgeo = g;
+  const bool x_ok = fast && rank_path(&v, RP_MFMA) == RP_MFMA;
+  const bool tile_ok = fast && rank_path(&v, RP_TILE) == RP_TILE;
+  if (requested == RP_MFMA) return x_ok ? RP_MFMA : -1;
+  if (requested == RP_TILE) return tile_ok ? RP_TILE : -1;
+  return x_ok ? RP_MFMA : (tile_ok ? RP_TILE : RP_SCAN);
+}
+
+struct ShardFastWs {
+  float *stats, *q, *qref, *s_true, *delta;
+  uint16_t *es, *qs;  // split-bf16 operands of the own rows and of q (path 1)
+  int64_t* state;
+  int32_t *gt, *ucnt, *ulist;
+  uint32_t* bits;
+};
+ShardFastWs carve_shard_fast(void* ws, const kge_model_desc* m, int64_t rows, int64_t nq, int rp, size_t* bytes) {
+  Carver c(ws);
+  ShardFastWs w;
+  const bool xs = rp == RP_MFMA;
+  w.stats = c.take<float>(TS_NSTAT * (1 + TS_BLOCKS));
+  w.es = c.take<uint16_t>(xs ? xsplit_elems(rows, m->entity_dim) : 0);
+  w.qs = c.take<uint16_t>(xs ? xsplit_elems(nq, m->entity_dim) : 0);
+  w.q = c.take<float>(nq * (int64_t)m->entity_dim);
+  w.qref = c.take<float>(nq * (int64_t)m->entity_dim);
+  w.s_true = c.take<float>(nq);
+  w.delta = c.take<float>(nq);
+  w.state = c.take<int64_t>(nq);
+  w.gt = c.take<int32_t>(2 * nq);  // gt | ucnt (zeroed by k_rsf_prep)
+  w.ucnt = w.gt ? w.gt + nq : nullptr;
+  w.ulist = c.take<int32_t>(nq * (int64_t)RANK_CAP);
+  w.bits = c.take<uint32_t>(nq * ((rows + 31) / 32));
+  *bytes = c.off + 256;
+  return w;
+}
+
+// The checks every call of the entry makes before it resolves the path, in
+// kge_rank_shard's order; *path = the requested path.
+int shard_fast_check(const kge_model_desc* m, int32_t mode, const kge_rank_shard_desc* sh, Geom* geo, int* path) {
+  int st = check_model(m, geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  if (!sh) return KGE_ERR_ARG;
+  if (sh->struct_size != (int32_t)sizeof(kge_rank_shard_desc)) return KGE_ERR_ABI;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
+  if (sh->flags & ~(7 | KGE_RANK_FILTER_TABLE)) return KGE_ERR_ARG;
+  *path = sh->flags & 7;
+  if (*path > RP_MFMA32) return KGE_ERR_ARG;
+  return KGE_OK;
+}
+
+int rank_shard_fast_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_desc* sh, const int64_t* queries,
+                         int64_t nq, int32_t* listed_out, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                         void* stream) {
+  Geom geo, fgeo;
+  int path = 0;
+  int st = shard_fast_check(m, mode, sh, &geo, &path);
+  if (st) return st;
+  if (!queries || !err_flag || nq < 0) return KGE_ERR_ARG;
+  if (!sh->fixed_rows || !sh->s_true || !sh->counts || !sh->filt_off || !sh->filt_ids) return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  const int rp = shard_fast_path(m, sh, path, &fgeo);
+  hipStream_t s = as_stream(stream);
+  if (rp == RP_SCAN) {  // the exact stage's own kernel, grid rule and workspace
+    kge_rank_shard_desc x = *sh;
+    x.flags = sh->flags & KGE_RANK_FILTER_TABLE;
+    st = rank_shard_impl(m, mode, &x, KGE_RSHARD_COUNT, queries, nq, workspace, workspace_bytes, err_flag, stream);
+    if (st || !listed_out) return st;
+    return launch_status(launch_zero(listed_out, nq, s));
+  }
+  if (rp > 0 && nq > 65535) return KGE_ERR_DIM;  // the bitmap and tile launches put queries on grid.y
+  if (rp < 0) return KGE_ERR_ARG;                // the requested fast pass cannot take these rows
+  const int64_t rows = sh->own_end - sh->own_begin;
+  const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
+  size_t need = 0;
+  const ShardFastWs w = carve_shard_fast(workspace, m, rows, nq, rp, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  const ModelOps& ops = ops_for(m->model);
+  const int md = kernel_mode(mode);
+  const int K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  const int64_t W = (rows + 31) / 32;
+  ShardFastArgs a;
+  memset(&a, 0, sizeof(a));
+  RefArgs& f = a.r;
+  f.ent = v.entity_embedding; f.rel = m->relation_embedding; f.modulus = m->modulus;
+  f.queries = queries; f.nq = nq; f.E = rows; f.R = m->nrelation;
+  f.Le = m->entity_dim; f.Lr = m->relation_dim; f.K = K; f.c = consts_of(m);
+  f.q = w.q; f.qref = w.qref; f.true_id = w.state; f.s_true = w.s_true;
+  f.true_exact = 1;  // s_true is the reduced reference-order score: δ covers the candidate's error only
+  f.delta = w.delta; f.stats = w.stats;
+  // TransE on the register tile: q from the same row bits by the same build_q, the tile's sequential sum
+  // from 0 — the bits ref_score_half gave s_true: δ = 0, exact ties are listed
+  f.exact_fast = (m->model == KGE_TRANSE && rp == RP_TILE) ? 1 : 0;
+  f.ucnt = w.ucnt; f.ulist = w.ulist; f.cap = RANK_CAP;
+  f.fbits = w.bits; f.W = W; f.gt = w.gt; f.err = err_flag;
+  f.trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
+  f.fast_u = (rp != RP_MFMA) ? 0.f : (float)(98.8 + 1.02 * xsplit_nslab(m->entity_dim));  // (as rank_bind)
+  a.eg = fgeo.eg; a.fixed_rows = sh->fixed_rows; a.s_true_in = sh->s_true;
+  a.own_lo = sh->own_begin; a.E_glob = m->nentity;
+  a.q_w = w.q; a.s_true_w = w.s_true; a.state_w = w.state; a.gt_w = w.gt; a.ucnt_w = w.ucnt; a.bits_w = w.bits;
+  a.counts = sh->counts; a.listed = listed_out;
+  auto stage = [&](int k) { return launch_status(ops.rank_shard_fast(md, fgeo.vec, fgeo.ns, k, a, s)); };
+  // 1. the states, the fast q, zeroed counters
+  st = stage(0);
+  if (st) return st;
+  if (rows > 0) {  // (an empty shard: bad queries flagged above, zero counts below)
+    // 2. the shard's excluded rows (an id outside the table is no error here, as in the exact stage)
+    st = launch_status(launch_filter_bits_range(queries, mode == KGE_HEAD_BATCH ? 1 : 0,
+                                                (sh->flags & KGE_RANK_FILTER_TABLE) ? 1 : 0, sh->filt_off,
+                                                sh->filt_ids, nq, m->nentity, m->nrelation, sh->own_begin,
+                                                sh->own_end, w.bits, nullptr, s));
+    if (st) return st;
+    // 3. the shard's statistics (and split operands), recomputed every call
+    if (rp == RP_MFMA) {
+      st = launch_status(launch_split_stats(v.entity_embedding, rows, m->entity_dim, w.es, w.stats, s, nullptr, nullptr));
+      if (!st) st = launch_status(launch_split_bf16(w.q, nq, m->entity_dim, w.qs, s));
+    } else if (m->model == KGE_DISTMULT || m->model == KGE_COMPLEX) {
+      st = launch_status(launch_table_stats(v.entity_embedding, rows, m->entity_dim, w.stats, s));
+    }
+    if (st) return st;
+    // 4. the true row's bit, the windows and the reference-order q
+    st = stage(1);
+    if (st) return st;
+    // 5. counting on the view: clear cases counted, near-ties listed
+    const RankWin win{w.delta, w.ucnt, w.ulist, RANK_CAP};
+    if (rp == RP_MFMA) {
+      st = launch_status(launch_rank_mfma_x(0, w.qs, w.es, nq, rows, m->entity_dim, w.state, w.s_true, w.bits, w.gt,
+                                            win, s));
+    } else {
+      TileArgs ta;
+      memset(&ta, 0, sizeof(ta));
+      ta.q = w.q; ta.ent = v.entity_embedding; ta.modulus = m->modulus;
+      ta.nq = nq; ta.E = rows; ta.Le = m->entity_dim; ta.K = K;
+      ta.c = f.c; ta.true_id = w.state; ta.s_true = w.s_true;
+      ta.fbits = w.bits; ta.W = W; ta.gt = w.gt; ta.win = win;
+      st = launch_status(ops.rank_tile(md, 0, ta, s));
+    }
+    if (st) return st;
+  }
+  // 6, 7. the listed candidates (an overflowed list: the own rows) in reference order; the counts
+  return stage(2);
+}
+
 }  // namespace
 }  // namespace kge
 
@@ -2476,6 +2634,34 @@ int kge_rank_shard(const kge_model_desc* m, int32_t mode, const kge_rank_shard_d
                    const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
                    void* stream) {
   return rank_shard_impl(m, mode, sh, stage, queries, nq, workspace, workspace_bytes, err_flag, stream);
+}
+
+// 1, 2 or 3; refused: minus the status the call returns for it
+int kge_rank_shard_fast_path(const kge_model_desc* m, const kge_rank_shard_desc* sh) {
+  Geom geo;
+  int path = 0;
+  // (the mode plays no part in the path)
+  const int st = shard_fast_check(m, KGE_HEAD_BATCH, sh, &geo, &path);
+  if (st) return -st;
+  if (!sh->fixed_rows) return -KGE_ERR_ARG;
+  const int rp = shard_fast_path(m, sh, path, nullptr);
+  return rp < 0 ? -KGE_ERR_ARG : rp;
+}
+
+// 0: a bad model, descriptor, range, flags, path or nq (the call itself says which)
+size_t kge_rank_shard_fast_workspace_bytes(const kge_model_desc* m, const kge_rank_shard_desc* sh, int64_t nq) {
+  const int rp = kge_rank_shard_fast_path(m, sh);
+  if (rp < 0 || nq < 0) return 0;
+  size_t b = 0;
+  if (rp == RP_SCAN) carve_shard(nullptr, m, nq, &b);
+  else carve_shard_fast(nullptr, m, sh->own_end - sh->own_begin, nq, rp, &b);
+  return b;
+}
+
+int kge_rank_shard_fast(const kge_model_desc* m, int32_t mode, const kge_rank_shard_desc* sh, const int64_t* queries,
+                        int64_t nq, int32_t* listed_out, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                        void* stream) {
+  return rank_shard_fast_impl(m, mode, sh, queries, nq, listed_out, workspace, workspace_bytes, err_flag, stream);
 }
 
 // 0: a bad model, descriptor, stage, range, k or nq (the call itself says which)

@@ -103,7 +103,7 @@ int launch_topk_merge_shard(const TopkShardMergeArgs& a, hipStream_t s);
 // kge_topk_shard's exclusion bitmap over the rows [lo, hi) only (kge_rank_mfma.hip): bits [nq, W],
 // W = ceil((hi − lo) / 32), bit = id − lo.  tab != 0: off / ids are the whole filter index, looked up
 // by the query's key (head picks it); else per-query lists.  Ids of [0, E) outside the range set no
-// bit; ids outside [0, E) set KGE_DEVERR_INDEX.
+// bit; ids outside [0, E) set KGE_DEVERR_INDEX (err null — kge_rank_shard_fast — : nothing).
 int launch_filter_bits_range(const int64_t* queries, int head, int tab, const int64_t* off, const int64_t* ids,
                              int64_t nq, int64_t E, int64_t R, int64_t lo, int64_t hi, uint32_t* bits, int32_t* err,
                              hipStream_t s);

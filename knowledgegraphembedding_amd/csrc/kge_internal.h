@@ -458,6 +458,37 @@ inline int shard_slots(int Le, int qw = 1) {
   return k > 8 ? 8 : (k < 1 ? 0 : k);
 }
 
+// kge_rank_shard_fast: the fast counting pass on a shard-local view (k_rsf_prep,
+// k_rsf_window, the counting tiles, k_rsf_finish).  r is the refinement's
+// argument block over the VIEW: r.ent = the shard's first row, r.E = its row
+// count, every id local (global − own_lo).  r.true_id holds each query's state:
+// −1 a query with an id out of range, [0, r.E) the true row's local id, r.E the
+// true row is another rank's.  r.s_true is the workspace's copy of the caller's
+// reduced reference-order scores (NaN for a bad query), r.true_exact = 1.
+struct ShardFastArgs {
+  RefArgs r;
+  RowGeom eg;               // k_rsf_prep's slots (by fixed_rows' and the relation table's alignment)
+  const float* fixed_rows;  // [nq, Le] the reduced fixed-side rows
+  const float* s_true_in;   // [nq] the reduced reference-order true scores
+  int64_t own_lo, E_glob;   // the shard's first row and the table's row count (global)
+  float* q_w;               // [nq, Le] = r.q        (k_rsf_prep writes)
+  float* s_true_w;          // [nq]     = r.s_true
+  int64_t* state_w;         // [nq]     = r.true_id
+  int32_t* gt_w;            // [nq]     = r.gt       (zeroed by k_rsf_prep)
+  int32_t* ucnt_w;          // [nq]     = r.ucnt     (k_rsf_window: cap + 1 for an infinite s_true, a rescan)
+  uint32_t* bits_w;         // [nq, W]  = r.fbits    (k_rsf_window adds the owned true row's bit)
+  int64_t* counts;          // [2, nq] strictly greater | equal (k_rsf_finish writes every place)
+  int32_t* listed;          // [nq] or null
+  int nslot;                // k_rsf_finish: half-waves with an LDS row slot (rsf_slots)
+  int in_place;             // k_rsf_finish: q and one slot do not fit LDS, rows are read where they lie
+};
+// k_rsf_finish's dynamic LDS, floats: [q: Lp][slots: nslot × Lp][2 counters, rounded to 4]
+inline int rsf_slots(int Le) {
+  const int Lp = (Le + 3) & ~3;
+  const int k = (65536 / 4 - Lp - 4) / Lp;
+  return k > 8 ? 8 : (k < 1 ? 0 : k);
+}
+
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {
   Pass = 0,       // q build + gather loop (k_row), with the epilogue in its tail when RowArgs.fuse_epi
@@ -493,6 +524,8 @@ struct ModelOps {
   int (*rank_cand)(int mode, const CandArgs&, hipStream_t);
   int (*rank_rel)(const RelRankArgs&, hipStream_t);
   int (*rank_shard)(int mode, int stage, const ShardArgs&, hipStream_t);  // stage: KGE_RSHARD_*
+  // kge_rank_shard_fast, stage 0: k_rsf_prep (vec / ns: fixed_rows' slots), 1: k_rsf_window, 2: k_rsf_finish
+  int (*rank_shard_fast)(int mode, int vec, int ns, int stage, const ShardFastArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

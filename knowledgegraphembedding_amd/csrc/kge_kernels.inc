@@ -2085,8 +2085,11 @@ int launch_topk_tile(int mode, const TopkTileArgs& b, hipStream_t s) {
 //              plus the interval's width, added there
 // TransE on the register tile is already the reference's sequence (same q,
 // same sequential sum from 0): δ = 0, only exact ties are listed.
+// (xrow: the anchor row where it is not the table's — kge_rank_shard_fast's
+// fixed_rows[q], whose owner may be another rank)
 template <int M, int MODE>
-__device__ __forceinline__ void rank_window_body(const RefArgs& a, int64_t qi, int64_t qrow) {
+__device__ __forceinline__ void rank_window_body(const RefArgs& a, int64_t qi, int64_t qrow,
+                                                 const float* xrow = nullptr) {
   constexpr bool CPLX = Traits<M>::cplx;
   const int lane = threadIdx.x & 63;
   if (a.true_id[qi] < 0) {
@@ -2097,7 +2100,7 @@ __device__ __forceinline__ void rank_window_body(const RefArgs& a, int64_t qi, i
   if constexpr (M == PROTATE) c.modulus = a.modulus[0];
   const int64_t h = a.queries[qrow * 3], r = a.queries[qrow * 3 + 1], t = a.queries[qrow * 3 + 2];
   const int64_t x = (MODE == HEAD_BATCH) ? t : h;
-  const float* xr = a.ent + x * a.Le;
+  const float* xr = xrow ? xrow : a.ent + x * a.Le;
   const float* rr = a.rel + r * a.Lr;
   const float* qf = a.q + qi * a.Le;
   float* qo = a.qref + qi * a.Le;
@@ -3573,6 +3576,191 @@ int launch_rank_shard(int mode, int stage, const ShardArgs& a, hipStream_t s) {
 #undef KGE_RSHARD_GO
 }
 
+// ------------------------- sharded filtered ranking, the fast counting pass
+// kge_rank_shard_fast: KGE_RSHARD_COUNT's counts from the single-table
+// pipeline's fast pass run on the shard's view (ShardFastArgs): the counting
+// tiles decide every owned candidate whose fast score clears the query's
+// window around the GIVEN reference-order s_true, and list the rest.
+//   k_rsf_prep     a wave per query: its state, the workspace's s_true, zeroed
+//                  counters, and the fast q from fixed_rows[q] with k_rank_prep's
+//                  load_row / build_q (RotatE with the caller's trig table: its
+//                  rotation, the reference q's bits).  No table row is read.
+//   k_rsf_window   a wave per query: the owned true row's bit into the shard's
+//                  bitmap, then rank_window_body with fixed_rows[q] as the
+//                  anchor row — the reference-order q and δ for true_exact.
+//   k_rsf_finish   a workgroup per query: the listed candidates (or, past the
+//                  list's cap, every owned row the bitmap leaves) scored in the
+//                  reference's order by its half-waves from their LDS row slots
+//                  and compared with s_true[q]; then the query's two counts.
+//                  The true row is no item here and is never read.
+template <int M, int MODE, int VEC, int NS>
+__global__ __launch_bounds__(256) void k_rsf_prep(ShardFastArgs a) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  using R_ = Row<NS, VEC, CPLX>;
+  const RefArgs& f = a.r;
+  const int lane = threadIdx.x & 63;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + wave_id();
+  if (qi >= f.nq) return;
+  Consts c = f.c;
+  if constexpr (M == PROTATE) c.modulus = f.modulus[0];
+  const int64_t h = f.queries[qi * 3], r = f.queries[qi * 3 + 1], t = f.queries[qi * 3 + 2];
+  const int64_t te = (MODE == HEAD_BATCH) ? h : t;
+  const bool bad = h < 0 || h >= a.E_glob || t < 0 || t >= a.E_glob || r < 0 || r >= f.R;
+  if (lane == 0) {
+    const int64_t tl = te - a.own_lo;
+    a.state_w[qi] = bad ? -1 : ((tl >= 0 && tl < f.E) ? tl : f.E);
+    a.s_true_w[qi] = bad ? NAN : a.s_true_in[qi];
+    a.gt_w[qi] = 0;
+    a.ucnt_w[qi] = 0;
+    if (bad) atomicOr(f.err, KGE_DEVERR_INDEX);
+  }
+  if (bad) return;
+  R_ q, xr, rr;
+  load_row<NS, VEC, CPLX>(a.fixed_rows + qi * f.Le, a.eg, lane, xr);
+  bool built = false;
+  if constexpr (M == ROTATE) {
+    if (f.trig) {  // (as k_rank_prep) q equals the window's reference q bit for bit
+      const float* tr = f.trig + r * 2 * f.Lr;
+      load_phase<NS, VEC>(tr, a.eg.S, lane, rr.a);
+      load_phase<NS, VEC>(tr + f.Lr, a.eg.S, lane, rr.b);
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+          Elem<M, MODE>::rotate(xr.a[s][v], xr.b[s][v], rr.a[s][v], rr.b[s][v], q.a[s][v], q.b[s][v]);
+      built = true;
+    }
+  }
+  if (!built) {
+    load_rel<M, NS, VEC, CPLX>(f.rel + r * f.Lr, a.eg, lane, rr);
+    build_q<M, MODE, NS, VEC, CPLX>(xr, rr, c, q);
+  }
+  store_row<NS, VEC, CPLX>(a.q_w + qi * f.Le, a.eg, lane, q);
+}
+
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rsf_window(ShardFastArgs a) {
+  const int64_t qi = (int64_t)blockIdx.x * 4 + wave_id();
+  if (qi >= a.r.nq) return;
+  const int64_t tl = a.r.true_id[qi];
+  if ((threadIdx.x & 63) == 0 && tl >= 0 && tl < a.r.E) atomicOr(&a.bits_w[qi * a.r.W + (tl >> 5)], 1u << (tl & 31));
+  rank_window_body<M, MODE>(a.r, qi, qi, a.fixed_rows + qi * a.r.Le);
+  // an infinite s_true: score − s_true is NaN for a score of the same infinity, which no window catches and the
+  // exact stage counts as a tie — mark the list as overflowed, so k_rsf_finish rescans the own rows
+  if ((threadIdx.x & 63) == 0 && tl >= 0 && __builtin_isinf(a.r.s_true[qi])) a.ucnt_w[qi] = a.r.cap + 1;
+}
+
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rsf_finish(ShardFastArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float fsm[];
+  const RefArgs& f = a.r;
+  const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
+  const int64_t qi = blockIdx.x;
+  const bool ok = f.true_id[qi] >= 0;  // (block-uniform)
+  const int n = ok ? f.ucnt[qi] : 0;
+  const int64_t gt0 = ok ? f.gt[qi] : 0;
+  if (n == 0) {  // nothing listed: the counting pass's count is final (a bad query: 0 / 0)
+    if (tid == 0) {
+      a.counts[qi] = gt0;
+      a.counts[f.nq + qi] = 0;
+      if (a.listed) a.listed[qi] = 0;
+    }
+    return;
+  }
+  Consts c = f.c;
+  if constexpr (M == PROTATE) c.modulus = f.modulus[0];
+  const int Le = f.Le, Lp = refine_lp(Le);
+  const int ns = a.in_place ? 8 : a.nslot;
+  float* slots = fsm + Lp;
+  int* cnt_s = reinterpret_cast<int*>(fsm + (a.in_place ? 0 : Lp * (1 + ns)));
+  const float* qr = f.qref + qi * Le;
+  if (!a.in_place)
+    for (int k = tid; k < Le; k += 256) fsm[k] = qr[k];
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  const float* qs = a.in_place ? qr : fsm;
+  const float st = f.s_true[qi];
+  const bool ovf = n > f.cap;  // the list overflowed: every owned row the bitmap leaves
+  const int64_t items = ovf ? f.E : (int64_t)n;
+  const int32_t* lst = f.ulist + qi * (int64_t)f.cap;
+  const uint32_t* bits = f.fbits + qi * f.W;
+  const bool vec4 = ((Le & 3) == 0) && ((((uintptr_t)f.ent) & 15) == 0);
+  int g = 0, e_ = 0;
+  if (half < ns) {
+    float* const row_l = slots + half * Lp;
+    for (int64_t j = half; j < items; j += ns) {
+      const int64_t e = ovf ? j : (int64_t)lst[j];
+      bool valid = e >= 0 && e < f.E;
+      if (ovf && valid) valid = ((bits[e >> 5] >> (e & 31)) & 1u) == 0u;
+      if (!valid) continue;  // (uniform in the half-wave, whose shuffles stay inside it)
+      const float* row = f.ent + e * Le;
+      if (!a.in_place) {
+        if (vec4) {
+          const float4* s4 = reinterpret_cast<const float4*>(row);
+          float4* r4 = reinterpret_cast<float4*>(row_l);
+          const int n4 = Le >> 2;
+          for (int k0 = hl; k0 < n4; k0 += 128) {  // four 16-B loads in flight per lane
+            const bool b1 = k0 + 32 < n4, b2 = k0 + 64 < n4, b3 = k0 + 96 < n4;
+            const float4 z = {0.f, 0.f, 0.f, 0.f};
+            const float4 v0 = s4[k0], v1 = b1 ? s4[k0 + 32] : z, v2 = b2 ? s4[k0 + 64] : z, v3 = b3 ? s4[k0 + 96] : z;
+            r4[k0] = v0;
+            if (b1) r4[k0 + 32] = v1;
+            if (b2) r4[k0 + 64] = v2;
+            if (b3) r4[k0 + 96] = v3;
+          }
+        } else {
+          for (int k0 = hl; k0 < Le; k0 += 128) {
+            const bool b1 = k0 + 32 < Le, b2 = k0 + 64 < Le, b3 = k0 + 96 < Le;
+            const float v0 = row[k0], v1 = b1 ? row[k0 + 32] : 0.f, v2 = b2 ? row[k0 + 64] : 0.f,
+                        v3 = b3 ? row[k0 + 96] : 0.f;
+            row_l[k0] = v0;
+            if (b1) row_l[k0 + 32] = v1;
+            if (b2) row_l[k0 + 64] = v2;
+            if (b3) row_l[k0 + 96] = v3;
+          }
+        }
+        // the half's lanes read each other's writes: one wave's LDS operations complete in order
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        row = row_l;
+      }
+      // (the score depends on every element of the row through the shuffles,
+      // so the row's reads are done before the next item overwrites it)
+      const float sc = ref_score_half<M, MODE>(qs, row, f.K, c, hl);
+      g += (sc > st);
+      e_ += (sc == st);
+    }
+    if (hl == 0 && (g | e_)) {  // integer sums: any order gives the same counts
+      atomicAdd(&cnt_s[0], g);
+      atomicAdd(&cnt_s[1], e_);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.counts[qi] = (ovf ? 0 : gt0) + cnt_s[0];
+    a.counts[f.nq + qi] = cnt_s[1];
+    if (a.listed) a.listed[qi] = n;
+  }
+}
+
+// stage 1 (k_rsf_window) and 2 (k_rsf_finish); stage 0 goes through the row dispatch (RunShardFast)
+template <int M>
+int launch_rank_shard_fast(int mode, int stage, const ShardFastArgs& a, hipStream_t s) {
+  if (stage == 1) {
+    hipLaunchKernelGGL(pick_dir(mode, k_rsf_window<M, HEAD_BATCH>, k_rsf_window<M, TAIL_BATCH>),
+                       dim3((unsigned)((a.r.nq + 3) / 4)), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+  }
+  if (stage != 2) return -1;
+  ShardFastArgs b = a;
+  const int Lp = refine_lp(a.r.Le);
+  b.nslot = rsf_slots(a.r.Le);
+  b.in_place = b.nslot == 0;
+  const size_t lds = sizeof(float) * (size_t)((b.in_place ? 0 : Lp * (1 + b.nslot)) + 4);
+  hipLaunchKernelGGL(pick_dir(mode, k_rsf_finish<M, HEAD_BATCH>, k_rsf_finish<M, TAIL_BATCH>), dim3((unsigned)a.r.nq),
+                     dim3(256), lds, s, b);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------ dispatch
 template <int M, int MODE, int VEC, int NS>
 struct Launch {
@@ -3743,8 +3931,24 @@ struct RunTopk {
   }
 };
 
+template <int M, int MODE, int VEC, int NS>
+struct RunShardFast {
+  static int run(int stage, const ShardFastArgs& a, hipStream_t s) {
+    if (stage != 0) return launch_rank_shard_fast<M>(MODE, stage, a, s);
+    if constexpr (NS == 0) {
+      return -1;  // rows wider than the register kernels hold: the entry resolves them to the exact stage
+    } else {
+      hipLaunchKernelGGL((k_rsf_prep<M, MODE, VEC, NS>), dim3((unsigned)((a.r.nq + 3) / 4)), dim3(256), 0, s, a);
+      return (int)hipGetLastError();
+    }
+  }
+};
+
 template <int M>
 struct ModelTable {
+  static int rank_shard_fast(int mode, int vec, int ns, int stage, const ShardFastArgs& a, hipStream_t s) {
+    return dispatch<M, RunShardFast>(mode, vec, ns, stage, a, s);
+  }
   static int score(int mode, int vec, int ns, const ScoreArgs& a, int64_t u, hipStream_t s) {
     return dispatch<M, RunScore>(mode, vec, ns, a, u, s);
   }
@@ -3779,6 +3983,7 @@ struct ModelTable {
     o.rank_cand = &launch_rank_cand<M>;                                                            \
     o.rank_rel = &launch_rank_rel<M>;                                                              \
     o.rank_shard = &launch_rank_shard<M>;                                                          \
+    o.rank_shard_fast = &ModelTable<M>::rank_shard_fast;                                           \
     return o;                                                                                      \
   }                                                                                                \
   }

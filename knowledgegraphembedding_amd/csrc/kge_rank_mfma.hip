@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void k_filter_bits_range(const int64_t* __rest
   for (int64_t p = b + tid; p < e_; p += 256) {
     const int64_t e = ids[p];
     if (e < 0 || e >= E) {
-      atomicOr(err, KGE_DEVERR_INDEX);
+      if (err) atomicOr(err, KGE_DEVERR_INDEX);  // (null: kge_rank_shard_fast, where such an id is no error)
       continue;
     }
     if (e < lo || e >= hi) continue;

@@ -670,12 +670,15 @@ def rank_relations(desc: _lib.ModelDesc, queries: torch.Tensor, dev, filt=None,
     return (ranks, ties, out_s) if scores else (ranks, ties)
 
 
-def _rank_shard(stage: int, name: str, desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, *,
-                fixed_rows: torch.Tensor, s_true: Optional[torch.Tensor] = None, filt=None,
-                filter_table: bool = False, counts: Optional[torch.Tensor] = None,
-                relation_trig: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
-    """One stage of kge_rank_shard on the caller's buffers (checked here: a
-    wrong-sized one is an out-of-bounds access on the device)."""
+def _rank_shard_desc(stage: int, name: str, desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, *,
+                     fixed_rows: torch.Tensor, s_true: Optional[torch.Tensor] = None, filt=None,
+                     filter_table: bool = False, counts: Optional[torch.Tensor] = None,
+                     relation_trig: Optional[torch.Tensor] = None):
+    """The checked arguments of one kge_rank_shard stage (and of
+    kge_rank_shard_fast, which takes COUNT's): (desc, queries on the device,
+    the kge_rank_shard_desc, the tensors it points into).  The caller's buffers
+    are checked here: a wrong-sized one is an out-of-bounds access on the
+    device."""
     if mode not in ("head-batch", "tail-batch"):
         raise ValueError("mode %s not supported" % mode)
     if relation_trig is not None:
@@ -712,6 +715,14 @@ def _rank_shard(stage: int, name: str, desc: _lib.ModelDesc, mode: str, queries:
         keep = (off, ids)
         sh.filt_off, sh.filt_ids = off.data_ptr(), ids.data_ptr()
         sh.flags = _lib.RANK_FILTER_TABLE if filter_table else 0
+    return desc, q, sh, keep
+
+
+def _rank_shard(stage: int, name: str, desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, *,
+                workspace: Optional[torch.Tensor] = None, **buffers) -> None:
+    """One stage of kge_rank_shard on the caller's buffers."""
+    desc, q, sh, keep = _rank_shard_desc(stage, name, desc, mode, queries, own, dev, **buffers)
+    nq = q.shape[0]
     lib = _lib.load()
     st = state(dev)
     ws = workspace if workspace is not None else st.workspace(lib.kge_rank_shard_workspace_bytes(desc, nq))
@@ -758,6 +769,69 @@ def rank_shard_count(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own
     _rank_shard(_lib.RSHARD_COUNT, "rank_shard_count", desc, mode, queries, own, dev, fixed_rows=fixed_rows,
                 s_true=s_true, filt=filt, filter_table=filter_table, counts=counts, relation_trig=relation_trig,
                 workspace=workspace)
+
+
+RANK_SHARD_FAST_PATHS = {"auto": 0, "mfma": 1, "tile": 2, "exact": 3}
+
+
+def rank_shard_fast_path(desc: _lib.ModelDesc, own, path: str = "auto", fixed_rows: Optional[torch.Tensor] = None,
+                         relation_trig: Optional[torch.Tensor] = None) -> int:
+    """The path rank_shard_count_fast takes on the shard own = (begin, end) of
+    `desc` (kge_rank_shard_fast_path): 1 split-bf16 MFMA tile, 2 register tile,
+    3 the exact stage's kernel.  ValueError for a path the shard's rows do not
+    admit.  `fixed_rows` / `relation_trig`: the call's own buffers, whose
+    alignment takes part (None: torch's, 16-byte aligned)."""
+    if path not in RANK_SHARD_FAST_PATHS:
+        raise ValueError("rank-shard path %s not supported" % path)
+    if relation_trig is not None:
+        desc = _lib.ModelDesc.from_buffer_copy(desc)
+        desc.relation_trig = relation_trig.data_ptr()
+    sh = _lib.RankShardDesc()
+    sh.own_begin, sh.own_end = int(own[0]), int(own[1])
+    sh.flags = RANK_SHARD_FAST_PATHS[path]
+    sh.fixed_rows = fixed_rows.data_ptr() if fixed_rows is not None else 256  # (only its alignment is looked at)
+    return _rank_shard_fast_resolve(desc, sh, path)
+
+
+def _rank_shard_fast_resolve(desc, sh, path: str) -> int:
+    rp = _lib.load().kge_rank_shard_fast_path(desc, sh)
+    if rp < 0:
+        raise ValueError(f"rank-shard path {path} refused for rows [{sh.own_begin}, {sh.own_end}) of this model: "
+                         + _lib.load().kge_status_string(-rp).decode())
+    return rp
+
+
+def rank_shard_count_fast(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev, fixed_rows: torch.Tensor,
+                          s_true: torch.Tensor, filt, counts: torch.Tensor, filter_table: bool = False,
+                          path: str = "auto", relation_trig: Optional[torch.Tensor] = None,
+                          listed: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """rank_shard_count by the fast counting pass (kge_rank_shard_fast): the
+    same arguments, the same `counts` bits.  The counting tiles decide every
+    owned row whose fast score clears the query's near-tie window around
+    s_true; the rest are scored in the reference's order.  `path`: "auto",
+    "mfma" (split-bf16 tile: DistMult, ComplEx), "tile" (register tile) or
+    "exact" (the exact stage's kernel); rank_shard_fast_path says which one
+    "auto" takes.  `listed` [nq] int32, optional: the rows of each query that
+    were scored in the reference's order.  At most 65535 queries on the fast
+    paths."""
+    if path not in RANK_SHARD_FAST_PATHS:
+        raise ValueError("rank-shard path %s not supported" % path)
+    desc, q, sh, keep = _rank_shard_desc(_lib.RSHARD_COUNT, "rank_shard_count_fast", desc, mode, queries, own, dev,
+                                         fixed_rows=fixed_rows, s_true=s_true, filt=filt, filter_table=filter_table,
+                                         counts=counts, relation_trig=relation_trig)
+    nq = q.shape[0]
+    sh.flags |= RANK_SHARD_FAST_PATHS[path]
+    if listed is not None and (listed.device != dev or listed.dtype != torch.int32 or not listed.is_contiguous()
+                               or listed.numel() != nq):
+        raise ValueError(f"rank_shard_count_fast: listed must be a contiguous int32 tensor of {nq} elements on {dev}")
+    if _rank_shard_fast_resolve(desc, sh, path) != RANK_SHARD_FAST_PATHS["exact"] and nq > 65535:
+        raise ValueError(f"rank_shard_count_fast: {nq} queries; the fast paths take at most 65535 per call")
+    lib = _lib.load()
+    st = state(dev)
+    ws = workspace if workspace is not None else st.workspace(lib.kge_rank_shard_fast_workspace_bytes(desc, sh, nq))
+    _lib.check(lib.kge_rank_shard_fast(desc, _lib.MODE_IDS[mode], sh, q.data_ptr(), nq, _ptr(listed), ws.data_ptr(),
+                                       ws.numel(), st.err.data_ptr(), _stream(dev)), "kge_rank_shard_fast")
+    del keep  # (the launches are queued on the stream the caching allocator frees behind)
 
 
 TOPK_MAX_K = 128  # kge_hip.h KGE_TOPK_MAX_K

@@ -411,6 +411,9 @@ class EntityRowPartition:
         bit for bit (RotatE with the reference's rotation table, as there;
         pRotatE with the correctly rounded device sin — test_step's library-sin
         form needs the near-tie lists of one table and is not available sharded).
+        The counts come from the fast counting pass (kge_rank_shard_fast: the
+        counting tiles on the shard, near-ties re-scored in reference order);
+        KGE_EVAL_SHARD_FAST=0 selects the exact stage, the same bits.
         `all_true_triples`: a triple list or a FilterIndex."""
         import numpy as np
         from . import ops
@@ -421,6 +424,7 @@ class EntityRowPartition:
         q = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
         desc, own = self._own_desc(model)
         table = index.device_table(mode, dev) if os.environ.get("KGE_RANK_FILTER_TABLE", "1") != "0" else None
+        fast = os.environ.get("KGE_EVAL_SHARD_FAST", "1") != "0"
         SUM = dist.ReduceOp.SUM
         ranks, ties = [], []
         with torch.no_grad():
@@ -437,8 +441,11 @@ class EntityRowPartition:
                 ops.rank_shard_true(desc, mode, qd, own, dev, fixed, s_true, relation_trig=trig)
                 dist.all_reduce(s_true.view(torch.int32), op=SUM, group=self.group)
                 counts = torch.empty(2, nq, dtype=torch.int64, device=dev)
-                ops.rank_shard_count(desc, mode, qd, own, dev, fixed, s_true, filt, counts,
-                                     filter_table=table is not None, relation_trig=trig)
+                # the fast counting pass (kge_rank_shard_fast) gives the exact stage's bits;
+                # KGE_EVAL_SHARD_FAST=0 selects the exact stage
+                count = ops.rank_shard_count_fast if fast else ops.rank_shard_count
+                count(desc, mode, qd, own, dev, fixed, s_true, filt, counts,
+                      filter_table=table is not None, relation_trig=trig)
                 dist.all_reduce(counts, op=SUM, group=self.group)
                 ranks.append(counts[0] + 1)
                 ties.append(counts[1])
