@@ -1459,20 +1459,57 @@ struct TopkWs {
   uint32_t* bits;
   int32_t* pid;
 };
-TopkWs carve_topk(void* ws, const kge_model_desc* m, int64_t nq, int k, int parts, size_t* bytes) {
+// v: the table the lists are taken over — the whole one (kge_topk, with qsan)
+// or a shard's view (kge_topk_shard's LIST; no rows: nothing but q and the states)
+TopkWs carve_topk(void* ws, const kge_model_desc* v, int64_t nq, int k, int parts, bool qsan, size_t* bytes) {
   Carver c(ws);
   TopkWs w;
-  const bool ph = m->model == KGE_PROTATE && rank_path(m, RP_TILE) == RP_TILE;
-  w.eph = c.take<float>(ph ? 2 * m->nentity * (int64_t)m->entity_dim : 0);
-  w.qph = c.take<float>(ph ? 2 * nq * (int64_t)m->entity_dim : 0);
-  w.q = c.take<float>(nq * (int64_t)m->entity_dim);
-  w.qsan = c.take<int64_t>(3 * nq);
+  const bool ph = v->nentity > 0 && v->model == KGE_PROTATE && rank_path(v, RP_TILE) == RP_TILE;
+  w.eph = c.take<float>(ph ? 2 * v->nentity * (int64_t)v->entity_dim : 0);
+  w.qph = c.take<float>(ph ? 2 * nq * (int64_t)v->entity_dim : 0);
+  w.q = c.take<float>(nq * (int64_t)v->entity_dim);
+  w.qsan = qsan ? c.take<int64_t>(3 * nq) : nullptr;
   w.state = c.take<int64_t>(nq);
-  w.bits = c.take<uint32_t>(nq * ((m->nentity + 31) / 32));
+  w.bits = c.take<uint32_t>(nq * ((v->nentity + 31) / 32));
   w.pscore = c.take<float>(nq * (int64_t)parts * k);
   w.pid = c.take<int32_t>(nq * (int64_t)parts * k);
   *bytes = c.off + 256;
   return w;
+}
+
+// The partial lists of a top-k call over the table (or shard view) v, whose
+// scan-kernel slots are vgeo's: each query's k best of every candidate part
+// into w.pscore / w.pid, from w.q, the states and the bitmap — on the register
+// tile (pRotatE: the phase tables first) or by the scan kernel.
+int topk_lists(const kge_model_desc* v, const Geom& vgeo, const TopkWs& w, int md, int64_t nq, int k, int parts,
+               int64_t span, bool tile, hipStream_t s) {
+  const ModelOps& ops = ops_for(v->model);
+  const int K = vgeo.cplx ? v->entity_dim / 2 : v->entity_dim;
+  const int64_t W = (v->nentity + 31) / 32;
+  const Consts c = consts_of(v);
+  if (!tile) {
+    TopkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ent = v->entity_embedding; a.modulus = v->modulus; a.nq = nq; a.E = v->nentity;
+    a.Le = v->entity_dim; a.eg = vgeo.eg; a.c = c;
+    a.q = w.q; a.state = w.state; a.fbits = w.bits; a.W = W;
+    a.k = k; a.parts = parts; a.span = span; a.pscore = w.pscore; a.pid = w.pid;
+    a.stage = 1;
+    return launch_status(ops.topk(md, vgeo.vec, vgeo.ns, a, s));
+  }
+  if (v->model == KGE_PROTATE) {
+    int st = launch_status(launch_prot_phase(v->entity_embedding, v->nentity, K, c.kappa_p, 1, w.eph, s));
+    if (!st) st = launch_status(launch_prot_phase(w.q, nq, K, 0.f, 0, w.qph, s));
+    if (st) return st;
+  }
+  TopkTileArgs b;
+  memset(&b, 0, sizeof(b));
+  b.t.q = w.q; b.t.ent = v->entity_embedding; b.t.modulus = v->modulus;
+  b.t.nq = nq; b.t.E = v->nentity; b.t.Le = v->entity_dim; b.t.K = K;
+  b.t.c = c; b.t.true_id = w.state; b.t.fbits = w.bits; b.t.W = W;
+  b.t.qph = w.qph; b.t.eph = w.eph;
+  b.k = k; b.parts = parts; b.span = span; b.pscore = w.pscore; b.pid = w.pid;
+  return launch_status(ops.topk_tile(md, b, s));
 }
 
 int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int64_t nq, const int64_t* filt_off,
@@ -1498,14 +1535,12 @@ int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
   int64_t span = 0;
   const int parts = topk_parts(m, nq, parts_req, &span);
   size_t need = 0;
-  const TopkWs w = carve_topk(workspace, m, nq, k, parts, &need);
+  const TopkWs w = carve_topk(workspace, m, nq, k, parts, true, &need);
   if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
 
   const ModelOps& ops = ops_for(m->model);
   hipStream_t s = as_stream(stream);
   const int md = kernel_mode(mode);
-  const bool cplx = (m->model == KGE_ROTATE || m->model == KGE_COMPLEX);
-  const int K = cplx ? m->entity_dim / 2 : m->entity_dim;
   const int64_t W = (m->nentity + 31) / 32;
   TopkArgs a;
   memset(&a, 0, sizeof(a));
@@ -1528,25 +1563,7 @@ int topk_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries, int
     st = launch_status(launch_filter_bits(filt_off, filt_ids, w.state, nq, m->nentity, w.bits, err_flag, s));
   if (st) return st;
   // 3. the partial lists
-  if (tile) {
-    const bool prot = m->model == KGE_PROTATE;
-    if (prot) {
-      st = launch_status(launch_prot_phase(m->entity_embedding, m->nentity, K, a.c.kappa_p, 1, w.eph, s));
-      if (!st) st = launch_status(launch_prot_phase(w.q, nq, K, 0.f, 0, w.qph, s));
-      if (st) return st;
-    }
-    TopkTileArgs b;
-    memset(&b, 0, sizeof(b));
-    b.t.q = w.q; b.t.ent = m->entity_embedding; b.t.modulus = m->modulus;
-    b.t.nq = nq; b.t.E = m->nentity; b.t.Le = m->entity_dim; b.t.K = K;
-    b.t.c = a.c; b.t.true_id = w.state; b.t.fbits = w.bits; b.t.W = W;
-    b.t.qph = w.qph; b.t.eph = w.eph;
-    b.k = k; b.parts = parts; b.span = span; b.pscore = w.pscore; b.pid = w.pid;
-    st = launch_status(ops.topk_tile(md, b, s));
-  } else {
-    a.stage = 1;
-    st = launch_status(ops.topk(md, geo.vec, geo.ns, a, s));
-  }
+  st = topk_lists(m, geo, w, md, nq, k, parts, span, tile, s);
   if (st) return st;
   // 4. the merge
   return launch_status(launch_topk_merge(w.pscore, w.pid, w.state, nq, parts, k, ids_out, scores_out, s));
@@ -1565,27 +1582,27 @@ kge_model_desc shard_view(const kge_model_desc* m, int64_t own_begin, int64_t ow
   return v;
 }
 
-struct TopkShardWs {
-  float *q, *qph, *eph, *pscore;
-  int64_t* state;
-  uint32_t* bits;
-  int32_t* pid;
-};
-// v: the shard's view; rows = its row count (0: nothing but q and the states)
-TopkShardWs carve_topk_shard(void* ws, const kge_model_desc* v, int64_t rows, int64_t nq, int k, int parts,
-                             size_t* bytes) {
-  Carver c(ws);
-  TopkShardWs w;
-  const bool ph = rows > 0 && v->model == KGE_PROTATE && rank_path(v, RP_TILE) == RP_TILE;
-  w.eph = c.take<float>(ph ? 2 * rows * (int64_t)v->entity_dim : 0);
-  w.qph = c.take<float>(ph ? 2 * nq * (int64_t)v->entity_dim : 0);
-  w.q = c.take<float>(nq * (int64_t)v->entity_dim);
-  w.state = c.take<int64_t>(nq);
-  w.bits = c.take<uint32_t>(nq * ((rows + 31) / 32));
-  w.pscore = c.take<float>(nq * (int64_t)parts * k);
-  w.pid = c.take<int32_t>(nq * (int64_t)parts * k);
-  *bytes = c.off + 256;
-  return w;
+// The model with `rows` (a shard entry's fixed_rows) for its entity table: *geo
+// = the slots of the kernels that read those rows, by THEIR alignment and the
+// relation table's.
+int fixed_view(const kge_model_desc* m, const float* rows, Geom* geo) {
+  kge_model_desc fv = *m;
+  fv.entity_embedding = rows;
+  return check_model(&fv, geo);
+}
+
+// The descriptor checks the shard entries share (D: kge_rank_shard_desc or
+// kge_topk_shard_desc), in the order their statuses are documented in: a null
+// descriptor, its struct_size, the entry's stage (stage_ok), the owned range,
+// the flags outside flag_mask.
+template <class D>
+int check_shard_desc(const D* sh, bool stage_ok, int64_t nentity, int32_t flag_mask) {
+  if (!sh) return KGE_ERR_ARG;
+  if (sh->struct_size != (int32_t)sizeof(D)) return KGE_ERR_ABI;
+  if (!stage_ok) return KGE_ERR_ARG;
+  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > nentity) return KGE_ERR_ARG;
+  if (sh->flags & ~flag_mask) return KGE_ERR_ARG;
+  return KGE_OK;
 }
 
 // the shard's parts (topk_parts over its rows; an empty shard has none)
@@ -1601,12 +1618,9 @@ int topk_shard_impl(const kge_model_desc* m, int32_t mode, const kge_topk_shard_
   int st = check_model(m, &geo);
   if (st) return st;
   if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!sh) return KGE_ERR_ARG;
-  if (sh->struct_size != (int32_t)sizeof(kge_topk_shard_desc)) return KGE_ERR_ABI;
   const bool list = stage == KGE_TSHARD_LIST;
-  if (!list && stage != KGE_TSHARD_MERGE) return KGE_ERR_ARG;
-  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
-  if (sh->flags & ~(7 | KGE_RANK_FILTER_TABLE)) return KGE_ERR_ARG;
+  st = check_shard_desc(sh, list || stage == KGE_TSHARD_MERGE, m->nentity, 7 | KGE_RANK_FILTER_TABLE);
+  if (st) return st;
   const int path = sh->flags & 7;
   if (path != RP_AUTO && path != RP_TILE && path != RP_SCAN) return KGE_ERR_ARG;  // (no MFMA top-k)
   if (sh->parts < 0) return KGE_ERR_ARG;
@@ -1642,17 +1656,14 @@ int topk_shard_impl(const kge_model_desc* m, int32_t mode, const kge_topk_shard_
   int64_t span = 0;
   const int parts = topk_shard_parts(&v, rows, nq, sh->parts, &span);
   size_t need = 0;
-  const TopkShardWs w = carve_topk_shard(workspace, &v, rows, nq, k, parts, &need);
+  const TopkWs w = carve_topk(workspace, &v, nq, k, parts, false, &need);
   if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
 
   const ModelOps& ops = ops_for(m->model);
-  const int K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
   const int64_t W = (rows + 31) / 32;
   // 1. q and each query's state, from fixed_rows (16-byte slots by ITS alignment and the relation table's)
-  kge_model_desc fv = *m;
-  fv.entity_embedding = sh->fixed_rows;
   Geom fgeo;
-  st = check_model(&fv, &fgeo);
+  st = fixed_view(m, sh->fixed_rows, &fgeo);
   if (st) return st;
   TopkArgs a;
   memset(&a, 0, sizeof(a));
@@ -1676,27 +1687,7 @@ int topk_shard_impl(const kge_model_desc* m, int32_t mode, const kge_topk_shard_
   if (rows > 0) {
     Geom vgeo;
     st = check_model(&v, &vgeo);
-    if (st) return st;
-    if (tile) {
-      if (m->model == KGE_PROTATE) {
-        st = launch_status(launch_prot_phase(v.entity_embedding, rows, K, a.c.kappa_p, 1, w.eph, s));
-        if (!st) st = launch_status(launch_prot_phase(w.q, nq, K, 0.f, 0, w.qph, s));
-        if (st) return st;
-      }
-      TopkTileArgs b;
-      memset(&b, 0, sizeof(b));
-      b.t.q = w.q; b.t.ent = v.entity_embedding; b.t.modulus = m->modulus;
-      b.t.nq = nq; b.t.E = rows; b.t.Le = m->entity_dim; b.t.K = K;
-      b.t.c = a.c; b.t.true_id = w.state; b.t.fbits = w.bits; b.t.W = W;
-      b.t.qph = w.qph; b.t.eph = w.eph;
-      b.k = k; b.parts = parts; b.span = span; b.pscore = w.pscore; b.pid = w.pid;
-      st = launch_status(ops.topk_tile(md, b, s));
-    } else {
-      a.ent = v.entity_embedding; a.E = rows; a.eg = vgeo.eg; a.fbits = w.bits; a.W = W;
-      a.k = k; a.parts = parts; a.span = span; a.pscore = w.pscore; a.pid = w.pid;
-      a.stage = 1;
-      st = launch_status(ops.topk(md, vgeo.vec, vgeo.ns, a, s));
-    }
+    if (!st) st = topk_lists(&v, vgeo, w, md, nq, k, parts, span, tile, s);
     if (st) return st;
   }
   // 4. the shard's list, global ids
@@ -1708,23 +1699,30 @@ int topk_shard_impl(const kge_model_desc* m, int32_t mode, const kge_topk_shard_
   return launch_status(launch_topk_merge_shard(g, s));
 }
 
-// ---- ranking against candidate lists (kge_rank_candidates)
-// The chunks of a query's list: one when the queries alone fill the device
-// (256 CUs × 8 workgroups), else enough to, of at least 64 candidates each and
-// at most CAND_CPC_MAX.  KGE_RANK_CAND_CHUNK (diagnostic): candidates per chunk;
-// the counts are integer sums, so no geometry changes a result.
-int64_t cand_chunks(int64_t nq, int64_t C, int* cpc) {
-  int64_t per = env_int("KGE_RANK_CAND_CHUNK", 0);
+// ---- the chunk rule of the row-walk entries (kge_rank_candidates,
+// kge_rank_relations, kge_rank_shard's COUNT)
+// The chunks of a query's n items (candidates of its list, relations, owned
+// rows): one when the queries alone fill the device (256 CUs × 8 workgroups),
+// else enough to, of at least 64 items each; *cpc = items per chunk, at most
+// cpc_max (the chunk's scores sit in LDS).  equal_floor: never fewer chunks
+// than cpc_max demands, so they come out of equal size (R = 1345 is 673 + 672,
+// not 1024 + 321: every chunk stages its fixed rows once more) — the candidate
+// lists go without it.  env_name (diagnostic): items per chunk; the counts are
+// integer sums, so no geometry changes a result.
+int64_t work_chunks(const char* env_name, int64_t nq, int64_t n, int cpc_max, bool equal_floor, int* cpc) {
+  int64_t per = env_int(env_name, 0);
   if (per < 1) {
-    const int64_t want = (2048 + nq - 1) / nq, most = (C + 63) / 64;
-    const int64_t chunks = want < most ? want : most;
-    per = (C + chunks - 1) / chunks;
+    const int64_t want = (2048 + nq - 1) / nq, most = (n + 63) / 64, least = (n + cpc_max - 1) / cpc_max;
+    int64_t chunks = want < most ? want : most;
+    if (equal_floor && chunks < least) chunks = least;
+    per = (n + chunks - 1) / chunks;
   }
-  if (per > CAND_CPC_MAX) per = CAND_CPC_MAX;
+  if (per > cpc_max) per = cpc_max;
   *cpc = (int)per;
-  return (C + per - 1) / per;
+  return (n + per - 1) / per;
 }
 
+// ---- ranking against candidate lists (kge_rank_candidates)
 struct CandWs {
   int32_t *gt, *eq;  // [nq] each, adjacent: one memset
   float* qref;       // [nq, Le], rows read in place only
@@ -1749,7 +1747,7 @@ int rank_cand_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries
   if (!queries || !cand || !ranks_out || !err_flag || nq < 0 || ncand < 1) return KGE_ERR_ARG;
   if (nq == 0) return KGE_OK;
   int cpc = 0;
-  const int64_t chunks = cand_chunks(nq, ncand, &cpc);
+  const int64_t chunks = work_chunks("KGE_RANK_CAND_CHUNK", nq, ncand, CAND_CPC_MAX, false, &cpc);
   if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // (query, chunk) work items on grid.x
   size_t need = 0;
   const CandWs w = carve_cand(workspace, m, nq, &need);
@@ -1777,25 +1775,6 @@ int rank_cand_impl(const kge_model_desc* m, int32_t mode, const int64_t* queries
 }
 
 // ---- relation prediction (kge_rank_relations)
-// The chunks of the relation range: all of R in one (up to REL_CPC_MAX) when
-// the queries alone fill the device (256 CUs × 8 workgroups), else enough to,
-// of at least 64 relations each; chunks of equal size (R = 1345 is 673 + 672,
-// not 1024 + 321: every chunk stages h and t once more).  KGE_RANK_REL_CHUNK
-// (diagnostic): relations per chunk; the counts are integer sums, so no
-// geometry changes a result.
-int64_t rel_chunks(int64_t nq, int64_t R, int* cpc) {
-  int64_t per = env_int("KGE_RANK_REL_CHUNK", 0);
-  if (per < 1) {
-    const int64_t want = (2048 + nq - 1) / nq, most = (R + 63) / 64, least = (R + REL_CPC_MAX - 1) / REL_CPC_MAX;
-    int64_t chunks = want < most ? want : most;
-    if (chunks < least) chunks = least;
-    per = (R + chunks - 1) / chunks;
-  }
-  if (per > REL_CPC_MAX) per = REL_CPC_MAX;
-  *cpc = (int)per;
-  return (R + per - 1) / per;
-}
-
 struct RelWs {
   int32_t *gt, *eq;  // [nq] each, adjacent: one memset
   float* trig;       // [R, 2, Lr], RotatE without a caller's table only
@@ -1822,7 +1801,7 @@ int rank_rel_impl(const kge_model_desc* m, const int64_t* queries, int64_t nq, c
   if ((filt_off == nullptr) != (filt_ids == nullptr)) return KGE_ERR_ARG;
   if (nq == 0) return KGE_OK;
   int cpc = 0;
-  const int64_t chunks = rel_chunks(nq, m->nrelation, &cpc);
+  const int64_t chunks = work_chunks("KGE_RANK_REL_CHUNK", nq, m->nrelation, REL_CPC_MAX, true, &cpc);
   if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // (query, chunk) work items on grid.x
   size_t need = 0;
   const RelWs w = carve_rel(workspace, m, nq, &need);
@@ -1861,24 +1840,6 @@ int rank_rel_impl(const kge_model_desc* m, const int64_t* queries, int64_t nq, c
 }
 
 // ---- sharded filtered ranking (kge_rank_shard)
-// The chunks of the owned range: equal sizes of at most SHARD_CPC_MAX rows, and
-// when the queries alone do not fill the device (256 CUs × 8 workgroups), more
-// of them, of at least 64 rows each.  KGE_RANK_SHARD_CHUNK (diagnostic): rows
-// per chunk; the counts are integer sums, so no geometry changes a result.
-int64_t shard_chunks(int64_t nq, int64_t rows, int* cpc) {
-  int64_t per = env_int("KGE_RANK_SHARD_CHUNK", 0);
-  if (per < 1) {
-    const int64_t want = (2048 + nq - 1) / nq, most = (rows + 63) / 64,
-                  least = (rows + SHARD_CPC_MAX - 1) / SHARD_CPC_MAX;
-    int64_t chunks = want < most ? want : most;
-    if (chunks < least) chunks = least;
-    per = (rows + chunks - 1) / chunks;
-  }
-  if (per > SHARD_CPC_MAX) per = SHARD_CPC_MAX;
-  *cpc = (int)per;
-  return (rows + per - 1) / per;
-}
-
 struct ShardWs {
   float* qref;  // [nq, Le], rows read in place only
 };
@@ -1897,11 +1858,9 @@ int rank_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_
   int st = check_model(m, &geo);
   if (st) return st;
   if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!sh) return KGE_ERR_ARG;
-  if (sh->struct_size != (int32_t)sizeof(kge_rank_shard_desc)) return KGE_ERR_ABI;
-  if (stage != KGE_RSHARD_ROWS && stage != KGE_RSHARD_TRUE && stage != KGE_RSHARD_COUNT) return KGE_ERR_ARG;
-  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
-  if (sh->flags != 0 && sh->flags != KGE_RANK_FILTER_TABLE) return KGE_ERR_ARG;
+  st = check_shard_desc(sh, stage == KGE_RSHARD_ROWS || stage == KGE_RSHARD_TRUE || stage == KGE_RSHARD_COUNT,
+                        m->nentity, KGE_RANK_FILTER_TABLE);
+  if (st) return st;
   if (!queries || !err_flag || nq < 0) return KGE_ERR_ARG;
   if (!sh->fixed_rows) return KGE_ERR_ARG;
   if (stage >= KGE_RSHARD_TRUE && !sh->s_true) return KGE_ERR_ARG;
@@ -1910,7 +1869,8 @@ int rank_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_
   const int64_t rows = sh->own_end - sh->own_begin;
   int cpc = 1;
   int64_t chunks = 1;  // (an empty shard: one chunk of no rows, which still flags the bad queries)
-  if (stage == KGE_RSHARD_COUNT && rows > 0) chunks = shard_chunks(nq, rows, &cpc);
+  if (stage == KGE_RSHARD_COUNT && rows > 0) 
+    chunks = work_chunks("KGE_RANK_SHARD_CHUNK", nq, rows, SHARD_CPC_MAX, true, &cpc);
   if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // queries (COUNT: (chunk, query) work items) on grid.x
   size_t need = 0;
   const ShardWs w = carve_shard(workspace, m, nq, &need);
@@ -1951,10 +1911,8 @@ int shard_fast_path(const kge_model_desc* m, const kge_rank_shard_desc* sh, int 
   if (requested == RP_SCAN) return RP_SCAN;
   if (requested < RP_AUTO || requested > RP_TILE) return -1;  // (the fp32 MFMA tile is not offered)
   const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
-  kge_model_desc fv = *m;
-  fv.entity_embedding = sh->fixed_rows;
   Geom g;
-  bool fast = m->model != KGE_PROTATE && check_model(&fv, &g) == KGE_OK && g.ns != 0;
+  bool fast = m->model != KGE_PROTATE && fixed_view(m, sh->fixed_rows, &g) == KGE_OK && g.ns != 0;
   if (fast && m->model == KGE_ROTATE && m->relation_trig && g.vec == 4 && !aligned16(m->relation_trig)) fast = false;
   if (fgeo) *fgeo = g;
   const bool x_ok = fast && rank_path(&v, RP_MFMA) == RP_MFMA;
@@ -1997,10 +1955,8 @@ int shard_fast_check(const kge_model_desc* m, int32_t mode, const kge_rank_shard
   int st = check_model(m, geo);
   if (st) return st;
   if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
-  if (!sh) return KGE_ERR_ARG;
-  if (sh->struct_size != (int32_t)sizeof(kge_rank_shard_desc)) return KGE_ERR_ABI;
-  if (sh->own_begin < 0 || sh->own_end < sh->own_begin || sh->own_end > m->nentity) return KGE_ERR_ARG;
-  if (sh->flags & ~(7 | KGE_RANK_FILTER_TABLE)) return KGE_ERR_ARG;
+  st = check_shard_desc(sh, true, m->nentity, 7 | KGE_RANK_FILTER_TABLE);
+  if (st) return st;
   *path = sh->flags & 7;
   if (*path > RP_MFMA32) return KGE_ERR_ARG;
   return KGE_OK;
@@ -2581,7 +2537,7 @@ size_t kge_topk_workspace_bytes(const kge_model_desc* m, int64_t nq, int32_t k, 
   if (check_model(m, &geo) || nq < 0 || k < 1 || k > KGE_TOPK_MAX_K || parts < 0) return 0;
   int64_t span = 0;
   size_t b = 0;
-  carve_topk(nullptr, m, nq, k, topk_parts(m, nq, parts, &span), &b);
+  carve_topk(nullptr, m, nq, k, topk_parts(m, nq, parts, &span), true, &b);
   return b;
 }
 
@@ -2678,7 +2634,7 @@ size_t kge_topk_shard_workspace_bytes(const kge_model_desc* m, const kge_topk_sh
   const kge_model_desc v = shard_view(m, sh->own_begin, sh->own_end);
   int64_t span = 0;
   size_t b = 0;
-  carve_topk_shard(nullptr, &v, rows, nq, sh->k, topk_shard_parts(&v, rows, nq, sh->parts, &span), &b);
+  carve_topk(nullptr, &v, nq, sh->k, topk_shard_parts(&v, rows, nq, sh->parts, &span), false, &b);
   return b;
 }
 

@@ -347,6 +347,20 @@ struct TopkTileArgs {
   int32_t* pid;
 };
 
+// LDS geometry of the staged row walk (kge_row_walk.inc), floats; the three
+// entries below share it.  A row slot is the row rounded to 4 floats;
+__host__ __device__ inline int refine_lp(int Le) { return (Le + 3) & ~3; }
+// a chunk's score array is 1 + cpc scores and 2 counters, rounded to 4;
+__host__ __device__ inline int walk_scrp(int cpc) { return (cpc + 1 + 2 + 3) & ~3; }
+// its exclusion bitmap is cpc bits, 32-bit words rounded to 4.
+__host__ __device__ inline int walk_bmw(int cpc) { return (((cpc + 31) >> 5) + 3) & ~3; }
+// Half-waves with an LDS row slot, at most 8: the slots share 64 KB with the
+// entry's fixed_floats; 0: not even one fits, rows are read in place.
+inline int walk_slots(int Le, int fixed_floats) {
+  const int k = (65536 / 4 - fixed_floats) / refine_lp(Le);
+  return k > 8 ? 8 : (k < 1 ? 0 : k);
+}
+
 // Ranking against per-query candidate lists (kge_rank_candidates; k_rank_cand,
 // k_rank_cand_q).  Work unit = (query, chunk of cpc candidates), chunk-minor on
 // grid.x; gt / eq are the workspace's per-query counters, zeroed by the call.
@@ -371,15 +385,8 @@ struct CandArgs {
   int32_t* err;
 };
 constexpr int CAND_CPC_MAX = 1024;  // candidates per chunk: the chunk's scores sit in LDS
-// k_rank_cand's LDS score array, floats: 1 + cpc scores and 2 counters, rounded to 4
-__host__ __device__ inline int cand_scrp(int cpc) { return (cpc + 1 + 2 + 3) & ~3; }
-// half-waves with an LDS row slot: q, the largest score array and the slots
-// (rows rounded to 4 floats) share 64 KB; 0: not even one fits, rows are read in place
-inline int cand_slots(int Le) {
-  const int Lp = (Le + 3) & ~3;
-  const int k = (65536 / 4 - Lp - cand_scrp(CAND_CPC_MAX)) / Lp;
-  return k > 8 ? 8 : (k < 1 ? 0 : k);
-}
+// fixed: q and the largest score array
+inline int cand_slots(int Le) { return walk_slots(Le, refine_lp(Le) + walk_scrp(CAND_CPC_MAX)); }
 
 // Relation prediction (kge_rank_relations; k_rank_rel).  Work unit = (query,
 // chunk of cpc consecutive relations), chunk-minor on grid.x; gt / eq are the
@@ -406,17 +413,9 @@ struct RelRankArgs {
   int32_t* err;
 };
 constexpr int REL_CPC_MAX = 1024;  // relations per chunk: the chunk's scores sit in LDS
-// k_rank_rel's LDS score array, floats: 1 + cpc scores and 2 counters, rounded to 4
-__host__ __device__ inline int rel_scrp(int cpc) { return (cpc + 1 + 2 + 3) & ~3; }
-// ... and its filter bitmap of cpc bits, 32-bit words rounded to 4
-__host__ __device__ inline int rel_bmw(int cpc) { return (((cpc + 31) >> 5) + 3) & ~3; }
-// half-waves with an LDS row slot: the h and t rows, the largest score array
-// and bitmap and the slots (rows rounded to 4 floats) share 64 KB; 0: not even
-// one slot fits, every row is read in place
+// fixed: the h and t rows, the largest score array and filter bitmap
 inline int rel_slots(int Le) {
-  const int Lp = (Le + 3) & ~3;
-  const int k = (65536 / 4 - 2 * Lp - rel_scrp(REL_CPC_MAX) - rel_bmw(REL_CPC_MAX)) / Lp;
-  return k > 8 ? 8 : (k < 1 ? 0 : k);
+  return walk_slots(Le, 2 * refine_lp(Le) + walk_scrp(REL_CPC_MAX) + walk_bmw(REL_CPC_MAX));
 }
 
 // Sharded filtered ranking (kge_rank_shard; k_rshard_rows, k_rshard_true,
@@ -449,13 +448,9 @@ struct ShardArgs {
   int32_t* err;
 };
 constexpr int SHARD_CPC_MAX = 1024;  // rows per chunk: the chunk's scores and its exclusion bitmap sit in LDS
-// half-waves with an LDS row slot: the q, largest score array and bitmap of
-// each of the workgroup's qw queries and the slots (rows rounded to 4 floats)
-// share 64 KB; 0: not even one fits (qw = 1: rows are read in place)
+// fixed: the q, largest score array and bitmap of each of the workgroup's qw queries
 inline int shard_slots(int Le, int qw = 1) {
-  const int Lp = (Le + 3) & ~3;
-  const int k = (65536 / 4 - qw * (Lp + cand_scrp(SHARD_CPC_MAX) + rel_bmw(SHARD_CPC_MAX))) / Lp;
-  return k > 8 ? 8 : (k < 1 ? 0 : k);
+  return walk_slots(Le, qw * (refine_lp(Le) + walk_scrp(SHARD_CPC_MAX) + walk_bmw(SHARD_CPC_MAX)));
 }
 
 // kge_rank_shard_fast: the fast counting pass on a shard-local view (k_rsf_prep,
@@ -483,11 +478,7 @@ struct ShardFastArgs {
   int in_place;             // k_rsf_finish: q and one slot do not fit LDS, rows are read where they lie
 };
 // k_rsf_finish's dynamic LDS, floats: [q: Lp][slots: nslot × Lp][2 counters, rounded to 4]
-inline int rsf_slots(int Le) {
-  const int Lp = (Le + 3) & ~3;
-  const int k = (65536 / 4 - Lp - 4) / Lp;
-  return k > 8 ? 8 : (k < 1 ? 0 : k);
-}
+inline int rsf_slots(int Le) { return walk_slots(Le, refine_lp(Le) + 4); }
 
 // What one ModelOps::row call launches (Launch::row, kge_kernels.inc / kge_wide.inc).
 enum class RowStage : int {

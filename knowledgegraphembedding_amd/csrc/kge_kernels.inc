@@ -2213,6 +2213,8 @@ __global__ __launch_bounds__(256) void k_rank_window(RefArgs a) {
   else rank_window_body<M, TAIL_BATCH>(a, qi, j);
 }
 
+#include "kge_row_walk.inc"
+
 // Refinement of the listed near-ties, one 256-thread block per query.  Work
 // item 0 is the true entity, items 1..n the listed candidates; the
 // half-waves with a staging slot take items j = half, half + nslot, ...  The
@@ -2230,7 +2232,6 @@ __global__ __launch_bounds__(256) void k_rank_window(RefArgs a) {
 // and decides every candidate whose interval clears the true one's; the
 // finish stage (sinv) scores the remaining items from the caller's sin
 // values.
-__host__ __device__ inline int refine_lp(int Le) { return (Le + 3) & ~3; }
 __host__ __device__ inline int refine_capp(int cap) { return (2 * (cap + 1) + 2 + 3) & ~3; }
 inline int refine_slots(int Le, int cap) {
   const int free_ = 65536 / 4 - refine_lp(Le) - refine_capp(cap);
@@ -2353,28 +2354,9 @@ __device__ __forceinline__ void rank_refine_body(const RefArgs& a, int64_t qi) {
         if (a.ref_global) {
           row = const_cast<float*>(src);  // read in place (never written)
         } else if (vec4) {
-          const float4* s4 = reinterpret_cast<const float4*>(src);
-          float4* r4 = reinterpret_cast<float4*>(row);
-          for (int k0 = hl; k0 < n4; k0 += 128) {  // four 16-B loads in flight per lane
-            const bool b1 = k0 + 32 < n4, b2 = k0 + 64 < n4, b3 = k0 + 96 < n4;
-            const float4 z = {0.f, 0.f, 0.f, 0.f};
-            const float4 v0 = s4[k0], v1 = b1 ? s4[k0 + 32] : z, v2 = b2 ? s4[k0 + 64] : z,
-                         v3 = b3 ? s4[k0 + 96] : z;
-            r4[k0] = v0;
-            if (b1) r4[k0 + 32] = v1;
-            if (b2) r4[k0 + 64] = v2;
-            if (b3) r4[k0 + 96] = v3;
-          }
+          stage_row<4>(src, row, n4, hl);
         } else {
-          for (int k0 = hl; k0 < Le; k0 += 128) {
-            const bool b1 = k0 + 32 < Le, b2 = k0 + 64 < Le, b3 = k0 + 96 < Le;
-            const float v0 = src[k0], v1 = b1 ? src[k0 + 32] : 0.f, v2 = b2 ? src[k0 + 64] : 0.f,
-                        v3 = b3 ? src[k0 + 96] : 0.f;
-            row[k0] = v0;
-            if (b1) row[k0 + 32] = v1;
-            if (b2) row[k0 + 64] = v2;
-            if (b3) row[k0 + 96] = v3;
-          }
+          stage_row<1>(src, row, Le, hl);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         score_item(j, row);
@@ -2426,19 +2408,9 @@ __device__ __forceinline__ void rank_refine_body(const RefArgs& a, int64_t qi) {
       return;
     }
   }
-  int g = 0, e_ = 0;
-  for (int j = 1 + tid; j <= n; j += 256) {
-    g += (scr[j] > st);
-    e_ += (scr[j] == st);
-  }
   if (tid < 2) cnt_s[tid] = 0;
   __syncthreads();
-  g = (int)wave_sum((float)g);  // counts ≤ cap: exact in fp32
-  e_ = (int)wave_sum((float)e_);
-  if ((tid & 63) == 0 && (g | e_)) {
-    atomicAdd(&cnt_s[0], g);
-    atomicAdd(&cnt_s[1], e_);
-  }
+  count_scores(scr + 1, n, st, cnt_s, [](int) { return false; });
   __syncthreads();
   if (tid == 0) {
     a.gt[qi] += cnt_s[0];
@@ -2743,36 +2715,44 @@ int launch_rank_ref(int mode, RefStage stage, const RefArgs& a, hipStream_t s) {
 // chunk-minor on grid.x.  The block builds the query's reference q in LDS
 // (ref_make_q, as k_rank_window), then its half-waves with a row slot walk the
 // items j = half, half + nslot, ...: item 0 is the true entity, items 1..n the
-// chunk's candidates.  A row is staged into the half's LDS slot from registers
-// that were loaded while the previous item was scored (the cascade of
-// ref_score_half reads its elements in a data-dependent order, so it reads LDS).
+// chunk's candidates, each row through the half's LDS slot (walk_rows).
 // The ids of a half's next 32 items sit one per lane, so a row's address never
 // waits for an id load.  Padding and out-of-range ids score the true row and
 // store NaN, which compares neither greater nor equal: a half-wave's shuffles
 // never diverge.  Scores land in LDS; the block counts them against item 0's
 // and adds its two integers to the query's counters.
-// Dynamic LDS, floats: [q: Lp][scores: 1 + cpc | 2 counters, cand_scrp][slots:
+// Dynamic LDS, floats: [q: Lp][scores: 1 + cpc | 2 counters, walk_scrp][slots:
 // nslot × Lp], Lp = refine_lp(Le).  Rows too wide for q and one slot (in_place)
 // are read where they lie and q comes from k_rank_cand_q's global copy
-// (cand_scrp, cand_slots: kge_internal.h).
+// (walk_scrp, cand_slots: kge_internal.h).
 
-// the query's reference-order q, element k by thread k mod 256 (k_rank_window's q)
+// a query's reference-order q from its fixed-side row xr, its relation row rr
+// and (RotatE, or null) the relation's [cos | sin] row tr, element k by thread
+// k mod 256 (k_rank_window's q)
+template <int M, int MODE>
+__device__ __forceinline__ void ref_build_q(const float* xr, const float* rr, const float* tr, int K, const Consts& c,
+                                            float* __restrict__ qo) {
+  constexpr bool CPLX = Traits<M>::cplx;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const float xa = xr[k], xb = CPLX ? xr[K + k] : 0.f;
+    const float ra = rr[k], rb = (M == COMPLEX) ? rr[K + k] : 0.f;
+    float qa, qb;
+    ref_make_q<M, MODE>(xa, xb, ra, rb, c, qa, qb, tr, k, K);
+    qo[k] = qa;
+    if constexpr (CPLX) qo[K + k] = qb;
+  }
+}
+// ... with the fixed side's row read from the table
 template <int M, int MODE>
 __device__ __forceinline__ void cand_build_q(const CandArgs& a, int64_t h, int64_t r, int64_t t, const Consts& c,
                                              float* __restrict__ qo) {
-  constexpr bool CPLX = Traits<M>::cplx;
-  const int64_t x = (MODE == HEAD_BATCH) ? t : h;
-  const float* xr = a.ent + x * a.Le;
-  const float* rr = a.rel + r * a.Lr;
-  const float* tr = (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr;
-  for (int k = threadIdx.x; k < a.K; k += 256) {
-    const float xa = xr[k], xb = CPLX ? xr[a.K + k] : 0.f;
-    const float ra = rr[k], rb = (M == COMPLEX) ? rr[a.K + k] : 0.f;
-    float qa, qb;
-    ref_make_q<M, MODE>(xa, xb, ra, rb, c, qa, qb, tr, k, a.K);
-    qo[k] = qa;
-    if constexpr (CPLX) qo[a.K + k] = qb;
-  }
+  ref_build_q<M, MODE>(a.ent + ((MODE == HEAD_BATCH) ? t : h) * a.Le, a.rel + r * a.Lr,
+                       (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr, a.K, c, qo);
+}
+
+// a query whose three ids lie in the tables
+__device__ __forceinline__ bool query_ok(int64_t E, int64_t R, int64_t h, int64_t r, int64_t t) {
+  return h >= 0 && h < E && t >= 0 && t < E && r >= 0 && r < R;
 }
 
 // TransE over a row staged in the half's own LDS slot: torch.norm(p=1) is one
@@ -2803,41 +2783,25 @@ __device__ __forceinline__ float cand_score_transe_lds(const float* __restrict__
   return ref_finish<TRANSE>(acc, c);
 }
 
-__device__ __forceinline__ bool cand_query_ok(const CandArgs& a, int64_t h, int64_t r, int64_t t) {
-  return h >= 0 && h < a.E && t >= 0 && t < a.E && r >= 0 && r < a.R;
-}
-
 // in_place only: q of every query into the workspace, one block per query
 template <int M, int MODE>
 __global__ __launch_bounds__(256) void k_rank_cand_q(CandArgs a) {
   const int64_t qi = blockIdx.x;
   const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
-  if (!cand_query_ok(a, h, r, t)) return;  // (k_rank_cand flags it)
+  if (!query_ok(a.E, a.R, h, r, t)) return;  // (k_rank_cand flags it)
   cand_build_q<M, MODE>(a, h, r, t, a.c, a.qref + qi * a.Le);
 }
 
-// VW: floats per staging slot — 4 (16-byte loads and LDS writes) or 1.
-// PQ: registers (slots) per lane of the prefetched next row — rows of at most
-// 32·PQ slots; 0: rows staged without prefetch, four loads in flight per lane
-// (as k_rank_refine's wide rows); −1: rows read in place.  Template
-// parameters, so each kernel scores at one place of its text (the half-wave
-// scoring is inlined there, and the prefetched row stays in registers: with
-// the variants chosen at run time inside one kernel it went to scratch).
-template <int VW>
-struct CandSlot { using T = float; };
-template <>
-struct CandSlot<4> { using T = tf4; };  // (a native vector: an array of HIP's float4 struct went to scratch)
-
+// PQ, VW: the shape of the row walk (walk_rows, kge_row_walk.inc; walk_variant picks them)
 template <int M, int MODE, int PQ, int VW>
 __global__ __launch_bounds__(256) void k_rank_cand(CandArgs a) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   constexpr bool IN_PLACE = PQ < 0;
-  using T = typename CandSlot<VW>::T;
   const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
   const int64_t qi = (int64_t)blockIdx.x / a.chunks;
   const int64_t ch = (int64_t)blockIdx.x - qi * a.chunks;
   const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
-  if (!cand_query_ok(a, h, r, t)) {  // (block-uniform) rank 0, ties 0: k_rank_cand_emit
+  if (!query_ok(a.E, a.R, h, r, t)) {  // (block-uniform) rank 0, ties 0: k_rank_cand_emit
     if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
     return;
   }
@@ -2850,7 +2814,7 @@ __global__ __launch_bounds__(256) void k_rank_cand(CandArgs a) {
   const int items = n + 1;
   float* scr = csm + (IN_PLACE ? 0 : Lp);
   int* cnt_s = reinterpret_cast<int*>(scr + a.cpc + 1);
-  float* slots = scr + cand_scrp(a.cpc);
+  float* slots = scr + walk_scrp(a.cpc);
   if constexpr (!IN_PLACE) cand_build_q<M, MODE>(a, h, r, t, c, csm);
   const float* qs = IN_PLACE ? a.qref + qi * Le : csm;
   if (tid < 2) cnt_s[tid] = 0;
@@ -2860,9 +2824,10 @@ __global__ __launch_bounds__(256) void k_rank_cand(CandArgs a) {
   if (half < ns) {
     // the half's i-th item is j = half + ns·i; lane hl holds the row id of item
     // i with i mod 32 = hl of the current group of 32: the true id for item 0
-    // and for a candidate that is not scored (my_ok = 0 then says "discard")
+    // and for a candidate that is not scored (my_ok = 0 then says "discard");
+    // walk_rows asks for i ascending, every i once
     int my_e = true_e, my_ok = 1;
-    auto item_id = [&](int i, bool& ok) __attribute__((always_inline)) -> int64_t {  // (i ascending, every i once)
+    auto item_src = [&](int i, bool& ok) __attribute__((always_inline)) -> const float* {
       if ((i & 31) == 0) {
         const int j = half + ns * (i + hl);
         my_e = true_e;
@@ -2876,86 +2841,18 @@ __global__ __launch_bounds__(256) void k_rank_cand(CandArgs a) {
       }
       const int src = ((tid & 32) + (i & 31)) << 2;
       ok = __builtin_amdgcn_ds_bpermute(src, my_ok) != 0;
-      return (int64_t)__builtin_amdgcn_ds_bpermute(src, my_e);
+      return a.ent + (int64_t)__builtin_amdgcn_ds_bpermute(src, my_e) * Le;
     };
-    auto score_item = [&](int j, float* row, bool ok) __attribute__((always_inline)) {
+    auto score = [&](int j, float* row, bool ok) __attribute__((always_inline)) {
       float sc;
       if constexpr (M == TRANSE && !IN_PLACE) sc = cand_score_transe_lds<MODE>(qs, row, a.K, c, hl);
       else sc = ref_score_half<M, MODE>(qs, row, a.K, c, hl);
       if (hl == 0) scr[j] = ok ? sc : NAN;
-      // (the score depends on every element of the row, so the row's reads are
-      // done before the next item overwrites it; the compiler keeps that order)
-      asm volatile("" ::: "memory");
     };
-    const int nit = (items - half + ns - 1) / ns;  // the half's items (≤ 0: none)
-    if constexpr (IN_PLACE) {
-      for (int i = 0; i < nit; ++i) {
-        bool ok;
-        const int64_t e = item_id(i, ok);
-        score_item(half + ns * i, const_cast<float*>(a.ent + e * Le), ok);  // read in place, never written
-      }
-    } else {
-      float* const row_l = slots + half * Lp;
-      const int nT = Le / VW;
-      T* const rT = reinterpret_cast<T*>(row_l);
-      const T zero = T();
-      if constexpr (PQ > 0) {
-        T nx[PQ > 0 ? PQ : 1];
-        bool nx_ok = true;
-        auto fetch = [&](int i) __attribute__((always_inline)) {
-          const T* sT = reinterpret_cast<const T*>(a.ent + item_id(i, nx_ok) * Le);
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            nx[u] = (k < nT) ? sT[k] : zero;
-          }
-        };
-        if (nit > 0) fetch(0);
-        for (int i = 0; i < nit; ++i) {
-          const bool ok = nx_ok;
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            if (k < nT) rT[k] = nx[u];
-          }
-          if (i + 1 < nit) fetch(i + 1);
-          // the half's 32 lanes read each other's writes: LDS operations of one
-          // wave complete in order, so waiting for this wave's writes suffices
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l, ok);
-        }
-      } else {
-        for (int i = 0; i < nit; ++i) {
-          bool ok;
-          const T* sT = reinterpret_cast<const T*>(a.ent + item_id(i, ok) * Le);
-          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
-            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
-            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
-                    v3 = b3 ? sT[k0 + 96] : zero;
-            rT[k0] = v0;
-            if (b1) rT[k0 + 32] = v1;
-            if (b2) rT[k0 + 64] = v2;
-            if (b3) rT[k0 + 96] = v3;
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l, ok);
-        }
-      }
-    }
+    walk_rows<PQ, VW>(items, half, ns, hl, slots + half * Lp, Le, item_src, score);
   }
   __syncthreads();
-  const float st = scr[0];
-  int g = 0, e_ = 0;
-  for (int j = 1 + tid; j <= n; j += 256) {
-    g += (scr[j] > st);
-    e_ += (scr[j] == st);
-  }
-  g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
-  e_ = (int)wave_sum((float)e_);
-  if ((tid & 63) == 0 && (g | e_)) {
-    atomicAdd(&cnt_s[0], g);
-    atomicAdd(&cnt_s[1], e_);
-  }
+  count_scores(scr + 1, n, scr[0], cnt_s, [](int) { return false; });
   __syncthreads();
   if (tid == 0) {  // integer sums: any order of the chunks gives the same counts
     if (cnt_s[0]) atomicAdd(&a.gt[qi], cnt_s[0]);
@@ -2972,26 +2869,14 @@ int launch_rank_cand(int mode, const CandArgs& a, hipStream_t s) {
     const int st = (int)hipGetLastError();
     if (st) return st;
   }
-  const size_t lds = sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (1 + a.nslot)) + cand_scrp(a.cpc));
+  const size_t lds = sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (1 + a.nslot)) + walk_scrp(a.cpc));
   const dim3 grid((unsigned)(a.nq * a.chunks));
-  auto go = [&](auto kh, auto kt) {
-    hipLaunchKernelGGL(pick_dir(mode, kh, kt), grid, dim3(256), lds, s, a);
+  return walk_variant(a.in_place, a.vec4, a.Le, [&](auto pq, auto vw) {
+    constexpr int PQ = decltype(pq)::value, VW = decltype(vw)::value;
+    hipLaunchKernelGGL(pick_dir(mode, k_rank_cand<M, HEAD_BATCH, PQ, VW>, k_rank_cand<M, TAIL_BATCH, PQ, VW>), grid,
+                       dim3(256), lds, s, a);
     return (int)hipGetLastError();
-  };
-  const int nT = a.vec4 ? a.Le >> 2 : a.Le;  // slots per row
-#define KGE_CAND_GO(PQ_, VW_) go(k_rank_cand<M, HEAD_BATCH, PQ_, VW_>, k_rank_cand<M, TAIL_BATCH, PQ_, VW_>)
-  if (a.in_place) return KGE_CAND_GO(-1, 1);
-  if (a.vec4) {
-    if (nT <= 128) return KGE_CAND_GO(4, 4);
-    if (nT <= 256) return KGE_CAND_GO(8, 4);
-    if (nT <= 512) return KGE_CAND_GO(16, 4);
-    return KGE_CAND_GO(0, 4);
-  }
-  if (nT <= 128) return KGE_CAND_GO(4, 1);
-  if (nT <= 256) return KGE_CAND_GO(8, 1);
-  if (nT <= 512) return KGE_CAND_GO(16, 1);
-  return KGE_CAND_GO(0, 1);
-#undef KGE_CAND_GO
+  });
 }
 
 // ------------------------------------------------- relation prediction
@@ -3013,8 +2898,8 @@ int launch_rank_cand(int mode, const CandArgs& a, hipStream_t s) {
 // filter list that fall into the chunk are marked in a bitmap of cpc bits; the
 // block counts the unmarked relations other than r against item 0, adds its two
 // integers to the query's counters and writes its slice of scores_out.
-// Dynamic LDS, floats: [h: Lp][t: Lp][scores: 1 + cpc | 2 counters, rel_scrp]
-// [bitmap: rel_bmw words][slots: nslot × Lp], Lp = refine_lp(Le) — a relation
+// Dynamic LDS, floats: [h: Lp][t: Lp][scores: 1 + cpc | 2 counters, walk_scrp]
+// [bitmap: walk_bmw words][slots: nslot × Lp], Lp = refine_lp(Le) — a relation
 // row, or RotatE's [cos | sin] row, is Le floats wide.  Rows too wide for h, t
 // and one slot (in_place) are all read where they lie (rel_slots:
 // kge_internal.h).
@@ -3096,18 +2981,18 @@ __device__ __forceinline__ float rel_score_transe_lds(const float* hs, const flo
   return ref_finish<TRANSE>(acc, c);
 }
 
-// PQ, VW: as k_rank_cand
+// PQ, VW: the shape of the row walk (walk_rows, kge_row_walk.inc)
 template <int M, int PQ, int VW>
 __global__ __launch_bounds__(256) void k_rank_rel(RelRankArgs a) {
   extern __shared__ __attribute__((aligned(16))) float rsm[];
   constexpr bool IN_PLACE = PQ < 0;
-  using T = typename CandSlot<VW>::T;
   const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
   const int64_t qi = (int64_t)blockIdx.x / a.chunks;
   const int64_t ch = (int64_t)blockIdx.x - qi * a.chunks;
   const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
   const int64_t j0 = ch * a.cpc;
   const int n = (int)((a.R - j0 < a.cpc) ? (a.R - j0) : a.cpc);  // ≥ 1
+  // (query_ok with r = −1, "no true relation", let through)
   if (!(h >= 0 && h < a.E && t >= 0 && t < a.E && r >= -1 && r < a.R)) {  // (block-uniform)
     if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
     if (a.scores)
@@ -3120,8 +3005,8 @@ __global__ __launch_bounds__(256) void k_rank_rel(RelRankArgs a) {
   const int items = n + 1;
   float* scr = rsm + (IN_PLACE ? 0 : 2 * Lp);
   int* cnt_s = reinterpret_cast<int*>(scr + a.cpc + 1);
-  uint32_t* bm = reinterpret_cast<uint32_t*>(scr + rel_scrp(a.cpc));
-  float* slots = scr + rel_scrp(a.cpc) + rel_bmw(a.cpc);
+  uint32_t* bm = reinterpret_cast<uint32_t*>(scr + walk_scrp(a.cpc));
+  float* slots = scr + walk_scrp(a.cpc) + walk_bmw(a.cpc);
   const float* hs = a.ent + h * Le;
   const float* ts = a.ent + t * Le;
   if constexpr (!IN_PLACE) {
@@ -3133,7 +3018,7 @@ __global__ __launch_bounds__(256) void k_rank_rel(RelRankArgs a) {
     ts = rsm + Lp;
   }
   if (tid < 2) cnt_s[tid] = 0;
-  for (int w = tid; w < rel_bmw(a.cpc); w += 256) bm[w] = 0u;
+  for (int w = tid; w < walk_bmw(a.cpc); w += 256) bm[w] = 0u;
   __syncthreads();
   if (a.filt_off && r >= 0) {  // the excluded ids of this chunk (any order, repeats, ids outside [0, R): harmless)
     const int64_t f1 = a.filt_off[qi + 1];
@@ -3147,85 +3032,25 @@ __global__ __launch_bounds__(256) void k_rank_rel(RelRankArgs a) {
   const int64_t r0 = r >= 0 ? r : 0;
   const int ns = IN_PLACE ? 8 : a.nslot;
   if (half < ns) {
-    auto item_row = [&](int i) -> const float* {  // the half's i-th item
+    auto item_row = [&](int i, bool&) __attribute__((always_inline)) -> const float* {  // the half's i-th item
       const int j = half + ns * i;
       return tab + (j == 0 ? r0 : j0 + j - 1) * Le;
     };
-    auto score_item = [&](int j, float* row) __attribute__((always_inline)) {
+    auto score = [&](int j, float* row, bool) __attribute__((always_inline)) {
       float sc;
       if constexpr (M == TRANSE && !IN_PLACE) sc = rel_score_transe_lds(hs, ts, row, a.K, c, hl);
       else sc = rel_score_half<M>(hs, ts, row, a.K, c, hl);
       if (hl == 0) scr[j] = sc;
-      // (the score depends on every element of the row: the row's reads are done
-      // before the next item overwrites it)
-      asm volatile("" ::: "memory");
     };
-    const int nit = (items - half + ns - 1) / ns;  // the half's items (≤ 0: none)
-    if constexpr (IN_PLACE) {
-      for (int i = 0; i < nit; ++i) score_item(half + ns * i, const_cast<float*>(item_row(i)));  // never written
-    } else {
-      float* const row_l = slots + half * Lp;
-      const int nT = Le / VW;
-      T* const rT = reinterpret_cast<T*>(row_l);
-      const T zero = T();
-      if constexpr (PQ > 0) {
-        T nx[PQ > 0 ? PQ : 1];
-        auto fetch = [&](int i) __attribute__((always_inline)) {
-          const T* sT = reinterpret_cast<const T*>(item_row(i));
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            nx[u] = (k < nT) ? sT[k] : zero;
-          }
-        };
-        if (nit > 0) fetch(0);
-        for (int i = 0; i < nit; ++i) {
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            if (k < nT) rT[k] = nx[u];
-          }
-          if (i + 1 < nit) fetch(i + 1);
-          // the half's lanes read each other's writes: one wave's LDS operations complete in order
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l);
-        }
-      } else {
-        for (int i = 0; i < nit; ++i) {
-          const T* sT = reinterpret_cast<const T*>(item_row(i));
-          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
-            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
-            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
-                    v3 = b3 ? sT[k0 + 96] : zero;
-            rT[k0] = v0;
-            if (b1) rT[k0 + 32] = v1;
-            if (b2) rT[k0 + 64] = v2;
-            if (b3) rT[k0 + 96] = v3;
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l);
-        }
-      }
-    }
+    walk_rows<PQ, VW>(items, half, ns, hl, slots + half * Lp, Le, item_row, score);
   }
   __syncthreads();
   if (a.scores)
     for (int j = 1 + tid; j <= n; j += 256) a.scores[qi * a.R + j0 + j - 1] = scr[j];
   if (r < 0) return;  // (block-uniform) prediction: no true relation, nothing to count
-  const float st = scr[0];
-  int g = 0, e_ = 0;
-  for (int j = 1 + tid; j <= n; j += 256) {
-    const int x = j - 1;
-    if (j0 + x == r || ((bm[x >> 5] >> (x & 31)) & 1u)) continue;  // the true relation itself; excluded
-    g += (scr[j] > st);
-    e_ += (scr[j] == st);
-  }
-  g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
-  e_ = (int)wave_sum((float)e_);
-  if ((tid & 63) == 0 && (g | e_)) {
-    atomicAdd(&cnt_s[0], g);
-    atomicAdd(&cnt_s[1], e_);
-  }
+  count_scores(scr + 1, n, scr[0], cnt_s, [&](int x) {  // the true relation itself; excluded
+    return j0 + x == r || ((bm[x >> 5] >> (x & 31)) & 1u) != 0u;
+  });
   __syncthreads();
   if (tid == 0) {  // integer sums: any order of the chunks gives the same counts
     if (cnt_s[0]) atomicAdd(&a.gt[qi], cnt_s[0]);
@@ -3237,24 +3062,12 @@ template <int M>
 int launch_rank_rel(const RelRankArgs& a, hipStream_t s) {
   const int Lp = refine_lp(a.Le);
   const size_t lds =
-      sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (2 + a.nslot)) + rel_scrp(a.cpc) + rel_bmw(a.cpc));
+      sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (2 + a.nslot)) + walk_scrp(a.cpc) + walk_bmw(a.cpc));
   const dim3 grid((unsigned)(a.nq * a.chunks));
-  auto go = [&](auto k) {
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
+  return walk_variant(a.in_place, a.vec4, a.Le, [&](auto pq, auto vw) {
+    hipLaunchKernelGGL((k_rank_rel<M, decltype(pq)::value, decltype(vw)::value>), grid, dim3(256), lds, s, a);
     return (int)hipGetLastError();
-  };
-  const int nT = a.vec4 ? a.Le >> 2 : a.Le;  // slots per row
-  if (a.in_place) return go(k_rank_rel<M, -1, 1>);
-  if (a.vec4) {
-    if (nT <= 128) return go(k_rank_rel<M, 4, 4>);
-    if (nT <= 256) return go(k_rank_rel<M, 8, 4>);
-    if (nT <= 512) return go(k_rank_rel<M, 16, 4>);
-    return go(k_rank_rel<M, 0, 4>);
-  }
-  if (nT <= 128) return go(k_rank_rel<M, 4, 1>);
-  if (nT <= 256) return go(k_rank_rel<M, 8, 1>);
-  if (nT <= 512) return go(k_rank_rel<M, 16, 1>);
-  return go(k_rank_rel<M, 0, 1>);
+  });
 }
 
 // ------------------------------------------- sharded filtered ranking
@@ -3283,33 +3096,19 @@ int launch_rank_rel(const RelRankArgs& a, hipStream_t s) {
 //                   ones are left out when the scores are counted against
 //                   s_true[q].  The two integers go to counts by atomics.
 // Dynamic LDS of k_rshard_count, floats: [q: Lp][scores: cpc | 2 counters,
-// cand_scrp][bitmap: rel_bmw][slots: nslot × Lp] (the first three QW times over
+// walk_scrp][bitmap: walk_bmw][slots: nslot × Lp] (the first three QW times over
 // with QW queries per workgroup).  Rows too wide for q and one
 // slot (in_place) are read where they lie and q comes from k_rshard_q's copy in
 // the workspace.
 
 __device__ __forceinline__ bool rshard_owned(const ShardArgs& a, int64_t e) { return e >= a.own_lo && e < a.own_hi; }
-__device__ __forceinline__ bool rshard_query_ok(const ShardArgs& a, int64_t h, int64_t r, int64_t t) {
-  return h >= 0 && h < a.E && t >= 0 && t < a.E && r >= 0 && r < a.R;
-}
 
-// the query's reference-order q from the reduced fixed-side row, element k by
-// thread k mod 256 (cand_build_q with the row given)
+// the query's reference-order q from the reduced fixed-side row (ref_build_q)
 template <int M, int MODE>
 __device__ __forceinline__ void rshard_build_q(const ShardArgs& a, int64_t qi, int64_t r, const Consts& c,
                                                float* __restrict__ qo) {
-  constexpr bool CPLX = Traits<M>::cplx;
-  const float* xr = a.fixed_rows + qi * a.Le;
-  const float* rr = a.rel + r * a.Lr;
-  const float* tr = (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr;
-  for (int k = threadIdx.x; k < a.K; k += 256) {
-    const float xa = xr[k], xb = CPLX ? xr[a.K + k] : 0.f;
-    const float ra = rr[k], rb = (M == COMPLEX) ? rr[a.K + k] : 0.f;
-    float qa, qb;
-    ref_make_q<M, MODE>(xa, xb, ra, rb, c, qa, qb, tr, k, a.K);
-    qo[k] = qa;
-    if constexpr (CPLX) qo[a.K + k] = qb;
-  }
+  ref_build_q<M, MODE>(a.fixed_rows + qi * a.Le, a.rel + r * a.Lr,
+                       (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr, a.K, c, qo);
 }
 
 template <int M, int MODE>
@@ -3333,7 +3132,7 @@ template <int M, int MODE>
 __global__ __launch_bounds__(256) void k_rshard_q(ShardArgs a) {
   const int64_t qi = blockIdx.x;
   const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
-  if (!rshard_query_ok(a, h, r, t)) return;  // (k_rshard_count flags it)
+  if (!query_ok(a.E, a.R, h, r, t)) return;  // (k_rshard_count flags it)
   rshard_build_q<M, MODE>(a, qi, r, a.c, a.qref + qi * a.Le);
 }
 
@@ -3344,7 +3143,7 @@ __global__ __launch_bounds__(256) void k_rshard_true(ShardArgs a) {
   const int64_t qi = blockIdx.x;
   const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
   const int64_t te = (MODE == HEAD_BATCH) ? h : t;
-  if (!rshard_query_ok(a, h, r, t) || !rshard_owned(a, te)) {  // (block-uniform)
+  if (!query_ok(a.E, a.R, h, r, t) || !rshard_owned(a, te)) {  // (block-uniform)
     if (tid == 0) reinterpret_cast<uint32_t*>(a.s_true)[qi] = 0u;
     return;
   }
@@ -3362,8 +3161,8 @@ __global__ __launch_bounds__(256) void k_rshard_true(ShardArgs a) {
   }
 }
 
-// PQ, VW: as k_rank_cand.  QW: queries per workgroup — every staged row is
-// scored against QW consecutive queries, whose q vectors, score arrays and
+// PQ, VW: the shape of the row walk (walk_rows).  QW: queries per workgroup —
+// every staged row is scored against QW consecutive queries, whose q vectors, score arrays and
 // bitmaps sit side by side in LDS (the same arithmetic per (query, row), 1 / QW
 // of the row reads; staged 16-byte rows of DistMult / ComplEx / RotatE /
 // pRotatE only: TransE's LDS sum overwrites the staged row).
@@ -3372,7 +3171,6 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
   extern __shared__ __attribute__((aligned(16))) float ssm[];
   constexpr bool IN_PLACE = PQ < 0;
   static_assert(QW == 1 || (!IN_PLACE && M != TRANSE), "several queries per workgroup: staged rows, not TransE");
-  using T = typename CandSlot<VW>::T;
   const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5;
   const int64_t groups = (a.nq + QW - 1) / QW;
   const int64_t ch = (int64_t)blockIdx.x / groups;  // chunk-major: neighbours on grid.x scan the same rows
@@ -3385,7 +3183,7 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
   const int Le = a.Le, Lp = refine_lp(Le);
   const int64_t e0 = a.own_lo + ch * a.cpc;  // the chunk's first row
   const int n = (int)((a.own_hi - e0 < a.cpc) ? (a.own_hi - e0) : a.cpc);  // (0: an empty shard's one chunk)
-  const int scrp = cand_scrp(a.cpc), bmw = rel_bmw(a.cpc);
+  const int scrp = walk_scrp(a.cpc), bmw = walk_bmw(a.cpc);
   float* const scr0 = ssm + (IN_PLACE ? 0 : QW * Lp);   // query w: scores scr0 + w·scrp (2 counters behind them),
   uint32_t* const bm0 = reinterpret_cast<uint32_t*>(scr0 + QW * scrp);  // bitmap bm0 + w·bmw, q at ssm + w·Lp
   float* slots = scr0 + QW * (scrp + bmw);
@@ -3399,7 +3197,7 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
     te[w] = 0;
     if (qi >= a.nq) continue;  // (the last group may be short)
     const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
-    if (!rshard_query_ok(a, h, r, t)) {
+    if (!query_ok(a.E, a.R, h, r, t)) {
       if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
       continue;
     }
@@ -3429,8 +3227,10 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
   const int ns = IN_PLACE ? 8 : a.nslot;
   if (half < ns) {
     // the half's i-th item is row j = half + ns·i of the chunk
-    auto item_row = [&](int i) -> const float* { return a.ent + (e0 + half + ns * i) * Le; };
-    auto score_item = [&](int j, float* row) __attribute__((always_inline)) {
+    auto item_row = [&](int i, bool&) __attribute__((always_inline)) -> const float* {
+      return a.ent + (e0 + half + ns * i) * Le;
+    };
+    auto score = [&](int j, float* row, bool) __attribute__((always_inline)) {
 #pragma unroll
       for (int w = 0; w < QW; ++w) {
         if (QW > 1 && !ok[w]) continue;  // (its q was not built)
@@ -3440,57 +3240,8 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
         else sc = ref_score_half<M, MODE>(qs, row, a.K, c, hl);
         if (hl == 0) scr0[w * scrp + j] = sc;
       }
-      // (the scores depend on every element of the row: the row's reads are done
-      // before the next item overwrites it)
-      asm volatile("" ::: "memory");
     };
-    const int nit = (n - half + ns - 1) / ns;  // the half's items (≤ 0: none)
-    if constexpr (IN_PLACE) {
-      for (int i = 0; i < nit; ++i) score_item(half + ns * i, const_cast<float*>(item_row(i)));  // never written
-    } else {
-      float* const row_l = slots + half * Lp;
-      const int nT = Le / VW;
-      T* const rT = reinterpret_cast<T*>(row_l);
-      const T zero = T();
-      if constexpr (PQ > 0) {
-        T nx[PQ > 0 ? PQ : 1];
-        auto fetch = [&](int i) __attribute__((always_inline)) {
-          const T* sT = reinterpret_cast<const T*>(item_row(i));
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            nx[u] = (k < nT) ? sT[k] : zero;
-          }
-        };
-        if (nit > 0) fetch(0);
-        for (int i = 0; i < nit; ++i) {
-#pragma unroll
-          for (int u = 0; u < PQ; ++u) {
-            const int k = hl + 32 * u;
-            if (k < nT) rT[k] = nx[u];
-          }
-          if (i + 1 < nit) fetch(i + 1);
-          // the half's lanes read each other's writes: one wave's LDS operations complete in order
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l);
-        }
-      } else {
-        for (int i = 0; i < nit; ++i) {
-          const T* sT = reinterpret_cast<const T*>(item_row(i));
-          for (int k0 = hl; k0 < nT; k0 += 128) {  // four loads in flight per lane
-            const bool b1 = k0 + 32 < nT, b2 = k0 + 64 < nT, b3 = k0 + 96 < nT;
-            const T v0 = sT[k0], v1 = b1 ? sT[k0 + 32] : zero, v2 = b2 ? sT[k0 + 64] : zero,
-                    v3 = b3 ? sT[k0 + 96] : zero;
-            rT[k0] = v0;
-            if (b1) rT[k0 + 32] = v1;
-            if (b2) rT[k0 + 64] = v2;
-            if (b3) rT[k0 + 96] = v3;
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          score_item(half + ns * i, row_l);
-        }
-      }
-    }
+    walk_rows<PQ, VW>(n, half, ns, hl, slots + half * Lp, Le, item_row, score);
   }
   __syncthreads();
 #pragma unroll
@@ -3498,20 +3249,9 @@ __global__ __launch_bounds__(256) void k_rshard_count(ShardArgs a) {
     if (!ok[w]) continue;
     const float* scr = scr0 + w * scrp;
     const uint32_t* bm = bm0 + w * bmw;
-    int* cnt_s = reinterpret_cast<int*>(scr0 + w * scrp + a.cpc);
-    const float st = a.s_true[qi0 + w];
-    int g = 0, e_ = 0;
-    for (int j = tid; j < n; j += 256) {
-      if ((bm[j >> 5] >> (j & 31)) & 1u) continue;  // the true entity itself; filtered
-      g += (scr[j] > st);
-      e_ += (scr[j] == st);
-    }
-    g = (int)wave_sum((float)g);  // counts ≤ cpc: exact in fp32
-    e_ = (int)wave_sum((float)e_);
-    if ((tid & 63) == 0 && (g | e_)) {
-      atomicAdd(&cnt_s[0], g);
-      atomicAdd(&cnt_s[1], e_);
-    }
+    count_scores(scr, n, a.s_true[qi0 + w], reinterpret_cast<int*>(scr0 + w * scrp + a.cpc), [&](int j) {
+      return ((bm[j >> 5] >> (j & 31)) & 1u) != 0u;  // the true entity itself; filtered
+    });
   }
   __syncthreads();
 #pragma unroll
@@ -3547,14 +3287,12 @@ int launch_rank_shard(int mode, int stage, const ShardArgs& a, hipStream_t s) {
   ShardArgs b = a;
   b.nslot = shard_slots(a.Le, qw);
   const size_t lds = sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (qw + b.nslot)) +
-                                              qw * (cand_scrp(a.cpc) + rel_bmw(a.cpc)));
+                                              qw * (walk_scrp(a.cpc) + walk_bmw(a.cpc)));
   const unsigned grid = (unsigned)(((a.nq + qw - 1) / qw) * a.chunks);
   auto launch_b = [&](auto kh, auto kt) {
     hipLaunchKernelGGL(pick_dir(mode, kh, kt), dim3(grid), dim3(256), lds, s, b);
     return (int)hipGetLastError();
   };
-#define KGE_RSHARD_GO(PQ_, VW_) \
-  launch_b(k_rshard_count<M, HEAD_BATCH, PQ_, VW_>, k_rshard_count<M, TAIL_BATCH, PQ_, VW_>)
 #define KGE_RSHARD_GOQ(PQ_, QW_) \
   launch_b(k_rshard_count<M, HEAD_BATCH, PQ_, 4, QW_>, k_rshard_count<M, TAIL_BATCH, PQ_, 4, QW_>)
   if constexpr (M != TRANSE) {
@@ -3562,18 +3300,10 @@ int launch_rank_shard(int mode, int stage, const ShardArgs& a, hipStream_t s) {
     if (qw == 4) return nT <= 128 ? KGE_RSHARD_GOQ(4, 4) : KGE_RSHARD_GOQ(8, 4);
   }
 #undef KGE_RSHARD_GOQ
-  if (a.in_place) return KGE_RSHARD_GO(-1, 1);
-  if (a.vec4) {
-    if (nT <= 128) return KGE_RSHARD_GO(4, 4);
-    if (nT <= 256) return KGE_RSHARD_GO(8, 4);
-    if (nT <= 512) return KGE_RSHARD_GO(16, 4);
-    return KGE_RSHARD_GO(0, 4);
-  }
-  if (nT <= 128) return KGE_RSHARD_GO(4, 1);
-  if (nT <= 256) return KGE_RSHARD_GO(8, 1);
-  if (nT <= 512) return KGE_RSHARD_GO(16, 1);
-  return KGE_RSHARD_GO(0, 1);
-#undef KGE_RSHARD_GO
+  return walk_variant(a.in_place, a.vec4, a.Le, [&](auto pq, auto vw) {
+    constexpr int PQ = decltype(pq)::value, VW = decltype(vw)::value;
+    return launch_b(k_rshard_count<M, HEAD_BATCH, PQ, VW>, k_rshard_count<M, TAIL_BATCH, PQ, VW>);
+  });
 }
 
 // ------------------------- sharded filtered ranking, the fast counting pass
@@ -3695,30 +3425,8 @@ __global__ __launch_bounds__(256) void k_rsf_finish(ShardFastArgs a) {
       if (!valid) continue;  // (uniform in the half-wave, whose shuffles stay inside it)
       const float* row = f.ent + e * Le;
       if (!a.in_place) {
-        if (vec4) {
-          const float4* s4 = reinterpret_cast<const float4*>(row);
-          float4* r4 = reinterpret_cast<float4*>(row_l);
-          const int n4 = Le >> 2;
-          for (int k0 = hl; k0 < n4; k0 += 128) {  // four 16-B loads in flight per lane
-            const bool b1 = k0 + 32 < n4, b2 = k0 + 64 < n4, b3 = k0 + 96 < n4;
-            const float4 z = {0.f, 0.f, 0.f, 0.f};
-            const float4 v0 = s4[k0], v1 = b1 ? s4[k0 + 32] : z, v2 = b2 ? s4[k0 + 64] : z, v3 = b3 ? s4[k0 + 96] : z;
-            r4[k0] = v0;
-            if (b1) r4[k0 + 32] = v1;
-            if (b2) r4[k0 + 64] = v2;
-            if (b3) r4[k0 + 96] = v3;
-          }
-        } else {
-          for (int k0 = hl; k0 < Le; k0 += 128) {
-            const bool b1 = k0 + 32 < Le, b2 = k0 + 64 < Le, b3 = k0 + 96 < Le;
-            const float v0 = row[k0], v1 = b1 ? row[k0 + 32] : 0.f, v2 = b2 ? row[k0 + 64] : 0.f,
-                        v3 = b3 ? row[k0 + 96] : 0.f;
-            row_l[k0] = v0;
-            if (b1) row_l[k0 + 32] = v1;
-            if (b2) row_l[k0 + 64] = v2;
-            if (b3) row_l[k0 + 96] = v3;
-          }
-        }
+        if (vec4) stage_row<4>(row, row_l, Le >> 2, hl);
+        else stage_row<1>(row, row_l, Le, hl);
         // the half's lanes read each other's writes: one wave's LDS operations complete in order
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         row = row_l;

@@ -80,10 +80,16 @@ WIDTHS = (Case("RotatE", 1000, nq=8, C=70), Case("DistMult", 600, nq=6, C=40), C
           Case("TransE", 203, nq=6, C=40), Case("TransE", 301, nq=6, C=40), Case("TransE", 2051, E=64, nq=4, C=20),
           Case("RotatE", 9000, E=64, nq=4, C=20))
 UNALIGNED = (Case("DistMult", 40, aligned=False), Case("RotatE", 20, aligned=False))
-PLANTED = tuple(Case(n, d, plant=True) for n, d in (("TransE", 37), ("DistMult", 40), ("ComplEx", 20), ("RotatE", 20)))
+# rows of exactly 128 | 129 slots, the first step of the prefetch ladder, of
+# both slot kinds (rank_relations_cases.BOUNDARY has 256 | 257, rank_shard_cases
+# 512 | 513 and over): two chunks of 35, more items than half-waves
+BOUNDARY = (Case("DistMult", 512, E=200, nq=5, C=70), Case("DistMult", 516, E=200, nq=5, C=70),
+            Case("DistMult", 128, E=200, nq=5, C=70, aligned=False), Case("DistMult", 129, E=200, nq=5, C=70))
+PLANTED =tuple(Case(n, d, plant=True) for n, d in (("TransE", 37), ("DistMult", 40), ("ComplEx", 20), ("RotatE", 20)))
 # one call past the 65,535-query ceiling of the other ranking entry points
 MANY = (Case("TransE", 8, E=50, nq=70001, C=3),)
-EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + LENGTHS + PADDED + WIDTHS + UNALIGNED + PLANTED + MANY
+EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + LENGTHS + PADDED + WIDTHS + UNALIGNED + BOUNDARY + \
+    PLANTED + MANY
 PROTATE_CASES = tuple(c for c in BASE if c.name == "pRotatE")
 ALL_CASES = EXACT_CASES + PROTATE_CASES
 

@@ -81,11 +81,16 @@ WIDTHS = (Case("RotatE", 1000, R=9, nq=8), Case("DistMult", 600, R=20, nq=6), Ca
           Case("TransE", 203, R=20, nq=6), Case("TransE", 301, R=20, nq=6), Case("TransE", 2051, R=12, E=64, nq=4),
           Case("RotatE", 9000, R=5, E=64, nq=4))
 UNALIGNED = (Case("DistMult", 40, aligned=False), Case("RotatE", 20, aligned=False), Case("TransE", 37, aligned=False))
+# relation rows of exactly 256 | 257 slots, the second step of the prefetch
+# ladder, of both slot kinds (rank_candidates_cases.BOUNDARY): two chunks of 35
+BOUNDARY = (Case("DistMult", 1024, R=70, E=200, nq=5), Case("DistMult", 1028, R=70, E=200, nq=5),
+            Case("DistMult", 256, R=70, E=200, nq=5, aligned=False), Case("DistMult", 257, R=70, E=200, nq=5))
 PLANTED = tuple(Case(n, d, plant=True) for n, d in (("TransE", 37), ("DistMult", 40), ("ComplEx", 20), ("RotatE", 20)))
-PRED = (Case("DistMult", 40, pred=True), Case("RotatE", 20, pred=True))
+PRED =(Case("DistMult", 40, pred=True), Case("RotatE", 20, pred=True))
 # one call past the 65,535-query ceiling of the other ranking entry points
 MANY = (Case("TransE", 8, R=3, E=50, nq=70001),)
-EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + COUNTS + WIDTHS + UNALIGNED + PLANTED + PRED + MANY
+EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + COUNTS + WIDTHS + UNALIGNED + BOUNDARY + \
+    PLANTED + PRED + MANY
 PROTATE_CASES = tuple(c for c in BASE if c.name == "pRotatE")
 ALL_CASES = EXACT_CASES + PROTATE_CASES
 

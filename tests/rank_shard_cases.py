@@ -88,9 +88,14 @@ BASE = (Case("TransE", 37, plant=True), Case("DistMult", 40, plant=True), Case("
 WIDTHS = (Case("RotatE", 1000, nq=8), Case("DistMult", 600, nq=6), Case("DistMult", 2400, E=64, nq=4),
           Case("RotatE", 9000, E=64, nq=4))
 UNALIGNED = (Case("DistMult", 40, aligned=False), Case("RotatE", 20, aligned=False))
+# rows of exactly 512 | 513 slots, the last step of the prefetch ladder
+# (rank_candidates_cases.BOUNDARY): 16-byte slots of 2048 | 2052 floats,
+# single-float slots of 512 | 516 floats on an unaligned table
+BOUNDARY = (Case("DistMult", 2048, E=200, nq=5), Case("DistMult", 2052, E=200, nq=5),
+            Case("DistMult", 512, E=200, nq=5, aligned=False), Case("DistMult", 516, E=200, nq=5, aligned=False))
 # one call past the 65,535-query ceiling of kge_rank_filtered*
 MANY = (Case("TransE", 8, E=50, nq=70001),)
-EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + WIDTHS + UNALIGNED + MANY
+EXACT_CASES = tuple(c for c in BASE if c.name != "pRotatE") + WIDTHS + UNALIGNED + BOUNDARY + MANY
 PROTATE_CASES = tuple(c for c in BASE if c.name == "pRotatE")
 ALL_CASES = EXACT_CASES + PROTATE_CASES
 FORMS = ("lists", "table")

@@ -93,6 +93,14 @@ def test_cases_cover_every_path():
             seen[(kind, 0 if n <= 128 else 1 if n <= 256 else 2 if n <= 512 else 3)] += 1
     assert all(v > 0 for v in seen.values()), seen
     assert max(c.nq for c in K.ALL_CASES) > 65535
+    # ... and a row of exactly the last slot count of each depth and of the next
+    # one up (four floats on for the widest single-float rows), between the three
+    # case tables whose kernels share the walk
+    import rank_relations_cases as KR
+    import rank_shard_cases as KS
+    exact = {slots(c)[:2] for c in K.ALL_CASES + KR.ALL_CASES + KS.ALL_CASES}
+    want = {(k, n) for k in ("v4", "f") for n in (128, 129, 256, 257, 512)} | {("v4", 513), ("f", 516)}
+    assert want <= exact, want - exact
 
 
 def test_true_lists_lookup():
