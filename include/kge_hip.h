@@ -993,6 +993,69 @@ int kge_rank_shard_fast(const kge_model_desc *m, int32_t mode, const kge_rank_sh
                         void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /*
+ * SHARDED RANKING AGAINST CANDIDATE LISTS — kge_rank_candidates over an entity
+ * table that is split into row shards, one per rank, evaluated in place: no
+ * rank ever holds another's rows.  The conventions are kge_rank_shard's:
+ * m->entity_embedding points own_begin rows BEFORE this rank's shard,
+ * m->nentity is the GLOBAL count, and only rows [own_begin, own_end) are read.
+ * Every rank passes the same queries and the same lists.  Per block of queries:
+ *   1. kge_rank_shard(KGE_RSHARD_ROWS)  → all-reduce(SUM) fixed_rows as int32;
+ *   2. kge_rank_shard(KGE_RSHARD_TRUE)  → all-reduce(SUM) s_true as int32;
+ *   3. this call                        → all-reduce(SUM) counts (int64);
+ *      rank = 1 + counts[0], ties = counts[1].
+ * (Stages 1 and 2 take a kge_rank_shard_desc; this call its own descriptor.)
+ *   counts[0][q] = #{j : own_begin <= cand[q,j] < own_end,
+ *                        score(cand[q,j]) > s_true[q]},
+ *   counts[1][q] the same with ==.
+ * "score" is the score of kge_rank_candidates: the mode's reference operation
+ * order, no fast pass, the same per-model exactness (RotatE reads
+ * m->relation_trig; pRotatE uses the correctly rounded device sin).  A rank is
+ * an integer count, so summed over a partition's shards the counts equal
+ * kge_rank_candidates' (rank − 1, ties) on the whole table, bit for bit.
+ *   Nothing is excluded: an owned copy of the true id is a tie, duplicates count
+ *   each time.  A negative id is padding.  An id >= nentity sets
+ *   KGE_DEVERR_INDEX and is skipped (every rank sees every list, so every rank
+ *   flags it); an id inside the table but outside the shard is simply not this
+ *   shard's.  A query with h, r or t out of range gets 0 / 0 and sets
+ *   KGE_DEVERR_INDEX, on an empty shard too; the other queries proceed.
+ *   own_begin == own_end is a valid empty shard: zero counts.
+ *   Rows of any width and alignment: 16-byte slots or single floats by the
+ *   alignment rule above (of the shard's first row and the relation table;
+ *   fixed_rows, s_true and relation_trig need float alignment only); rows too
+ *   wide to stage in LDS are read in place.  Queries go on grid.x: one call
+ *   takes any nq and ncand whose (query, list chunk) count stays below 2^31.
+ *   Each workgroup compacts the owned ids of its chunk of at most 1024 list
+ *   places and scores those alone, so a shard's work is its share of the
+ *   lists.  The counts are integer sums over the chunks: deterministic, and
+ *   independent of the launch geometry (KGE_RANK_CAND_SHARD_CHUNK, diagnostic:
+ *   list places per chunk).  Nothing allocates or synchronises; counts is
+ *   zeroed by a kernel and every place of it is written.
+ * Host checks, in this order: the model (as every entry); the mode (KGE_SINGLE:
+ * KGE_ERR_MODE); a NULL descriptor (KGE_ERR_ARG), then its struct_size
+ * (KGE_ERR_ABI); then KGE_ERR_ARG for own_begin > own_end or a range outside
+ * [0, nentity], flags other than 0, null queries / cand / err_flag /
+ * fixed_rows / s_true / counts, nq < 0 or ncand < 1; nq == 0 returns KGE_OK;
+ * more (query, chunk) work items than grid.x holds (KGE_ERR_DIM); the workspace
+ * (KGE_ERR_WORKSPACE).
+ * The workspace holds the queries' q vectors when rows are read in place, and
+ * nothing otherwise (a 256-byte minimum) — never an [nq, ncand] object.
+ * NOT pinned for this entry: graph capture, and tables past 2 GiB (row offsets
+ * are 64-bit, but no test runs it there).
+ */
+typedef struct kge_rank_cand_shard_desc {
+  int32_t struct_size;          /* = sizeof(kge_rank_cand_shard_desc) (else KGE_ERR_ABI) */
+  int32_t flags;                /* must be 0 */
+  int64_t own_begin, own_end;   /* global ids; own_begin == own_end is a valid empty shard */
+  const float *fixed_rows;      /* [nq, entity_dim], reduced output of KGE_RSHARD_ROWS */
+  const float *s_true;          /* [nq], reduced output of KGE_RSHARD_TRUE */
+  int64_t *counts;              /* [2, nq]: row 0 strictly greater, row 1 equal */
+} kge_rank_cand_shard_desc;
+size_t kge_rank_candidates_shard_workspace_bytes(const kge_model_desc *m, int64_t nq, int64_t ncand);
+int kge_rank_candidates_shard(const kge_model_desc *m, int32_t mode, const kge_rank_cand_shard_desc *sh,
+                              const int64_t *queries, int64_t nq, const int64_t *cand, int64_t ncand,
+                              void *workspace, size_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/*
  * SHARDED TOP-K LINK PREDICTION — kge_topk over an entity table that is split
  * into row shards, one per rank, predicted in place: no rank ever holds
  * another's rows.  The conventions are kge_rank_shard's: m->entity_embedding

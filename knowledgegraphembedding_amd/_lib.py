@@ -112,6 +112,18 @@ class RankShardDesc(C.Structure):
                 ("filt_ids", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class RankCandShardDesc(C.Structure):
+    """struct kge_rank_cand_shard_desc (sharded ranking against candidate lists, kge_rank_candidates_shard;
+    struct_size is set on construction)."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(RankCandShardDesc)
+
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("own_begin", C.c_int64), ("own_end", C.c_int64),
+                ("fixed_rows", C.c_void_p), ("s_true", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class TopkShardDesc(C.Structure):
     """struct kge_topk_shard_desc (sharded top-k, kge_topk_shard; struct_size is set on construction)."""
 
@@ -214,6 +226,9 @@ SIGNATURES = {
     "kge_rank_shard_fast_workspace_bytes": (_SZ, [_DESC, C.POINTER(RankShardDesc), _I64]),
     "kge_rank_shard_fast_path": (C.c_int, [_DESC, C.POINTER(RankShardDesc)]),
     "kge_rank_shard_fast": (C.c_int, [_DESC, _I32, C.POINTER(RankShardDesc), _P, _I64, _P, _P, _SZ, _P, _P]),
+    "kge_rank_candidates_shard_workspace_bytes": (_SZ, [_DESC, _I64, _I64]),
+    "kge_rank_candidates_shard": (C.c_int, [_DESC, _I32, C.POINTER(RankCandShardDesc), _P, _I64, _P, _I64, _P, _SZ,
+                                            _P, _P]),
     "kge_topk_shard_workspace_bytes": (_SZ, [_DESC, C.POINTER(TopkShardDesc), _I32, _I64]),
     "kge_topk_shard": (C.c_int, [_DESC, _I32, C.POINTER(TopkShardDesc), _I32, _P, _I64, _P, _SZ, _P, _P]),
     "kge_rank_sin_args": (C.c_int, [_DESC, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),

@@ -1901,6 +1901,58 @@ int rank_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_shard_
   return launch_status(ops_for(m->model).rank_shard(kernel_mode(mode), stage, a, s));
 }
 
+// ---- sharded ranking against candidate lists (kge_rank_candidates_shard)
+struct CandShardWs {
+  float* qref;  // [nq, Le], rows read in place only
+};
+CandShardWs carve_cand_shard(void* ws, const kge_model_desc* m, int64_t nq, size_t* bytes) {
+  Carver c(ws);
+  CandShardWs w;
+  w.qref = c.take<float>(cand_shard_slots(m->entity_dim) == 0 ? nq * (int64_t)m->entity_dim : 0);
+  *bytes = c.off + 256;
+  return w;
+}
+
+int rank_cand_shard_impl(const kge_model_desc* m, int32_t mode, const kge_rank_cand_shard_desc* sh,
+                         const int64_t* queries, int64_t nq, const int64_t* cand, int64_t ncand, void* workspace,
+                         size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  Geom geo;
+  int st = check_model(m, &geo);
+  if (st) return st;
+  if (mode != KGE_HEAD_BATCH && mode != KGE_TAIL_BATCH) return KGE_ERR_MODE;
+  st = check_shard_desc(sh, true, m->nentity, 0);
+  if (st) return st;
+  if (!queries || !cand || !err_flag || !sh->fixed_rows || !sh->s_true || !sh->counts || nq < 0 || ncand < 1)
+    return KGE_ERR_ARG;
+  if (nq == 0) return KGE_OK;
+  int cpc = 0;
+  const int64_t chunks = work_chunks("KGE_RANK_CAND_SHARD_CHUNK", nq, ncand, CAND_SHARD_CPC_MAX, false, &cpc);
+  if (nq > 0x7fffffff / chunks) return KGE_ERR_DIM;  // (query, chunk) work items on grid.x
+  size_t need = 0;
+  const CandShardWs w = carve_cand_shard(workspace, m, nq, &need);
+  if (!workspace || workspace_bytes < need) return KGE_ERR_WORKSPACE;
+
+  hipStream_t s = as_stream(stream);
+  CandShardArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ent = m->entity_embedding; a.rel = m->relation_embedding; a.modulus = m->modulus;
+  a.trig = (m->model == KGE_ROTATE) ? m->relation_trig : nullptr;
+  a.queries = queries; a.cand = cand; a.nq = nq; a.C = ncand; a.E = m->nentity; a.R = m->nrelation;
+  a.own_lo = sh->own_begin; a.own_hi = sh->own_end;
+  a.Le = m->entity_dim; a.Lr = m->relation_dim; a.K = geo.cplx ? m->entity_dim / 2 : m->entity_dim;
+  a.c = consts_of(m);
+  a.chunks = chunks; a.cpc = cpc;
+  // 16-byte slots by the header's rule: the row span a multiple of 4, both tables aligned
+  // (rows are then a multiple of 16 bytes, so the shard is aligned as its base pointer is)
+  a.vec4 = (a.K % 4 == 0) && aligned16(m->entity_embedding) && aligned16(m->relation_embedding);
+  a.nslot = cand_shard_slots(a.Le);
+  a.in_place = a.nslot == 0;
+  a.fixed_rows = sh->fixed_rows; a.s_true = sh->s_true; a.qref = w.qref; a.counts = sh->counts; a.err = err_flag;
+  st = launch_status(launch_zero(sh->counts, 4 * nq, s));  // [2, nq] int64
+  if (st) return st;
+  return launch_status(ops_for(m->model).rank_cand_shard(kernel_mode(mode), a, s));
+}
+
 // ---- sharded filtered ranking, the fast counting pass (kge_rank_shard_fast)
 // KGE_RSHARD_COUNT's counts from the single-table pipeline's fast pass on the
 // shard's view (shard_view, as kge_topk_shard): rank_path's rules applied to
@@ -2590,6 +2642,20 @@ int kge_rank_shard(const kge_model_desc* m, int32_t mode, const kge_rank_shard_d
                    const int64_t* queries, int64_t nq, void* workspace, size_t workspace_bytes, int32_t* err_flag,
                    void* stream) {
   return rank_shard_impl(m, mode, sh, stage, queries, nq, workspace, workspace_bytes, err_flag, stream);
+}
+
+size_t kge_rank_candidates_shard_workspace_bytes(const kge_model_desc* m, int64_t nq, int64_t ncand) {
+  Geom geo;
+  if (check_model(m, &geo) || nq < 0 || ncand < 1) return 0;
+  size_t b = 0;
+  carve_cand_shard(nullptr, m, nq, &b);
+  return b;
+}
+
+int kge_rank_candidates_shard(const kge_model_desc* m, int32_t mode, const kge_rank_cand_shard_desc* sh,
+                              const int64_t* queries, int64_t nq, const int64_t* cand, int64_t ncand, void* workspace,
+                              size_t workspace_bytes, int32_t* err_flag, void* stream) {
+  return rank_cand_shard_impl(m, mode, sh, queries, nq, cand, ncand, workspace, workspace_bytes, err_flag, stream);
 }
 
 // 1, 2 or 3; refused: minus the status the call returns for it

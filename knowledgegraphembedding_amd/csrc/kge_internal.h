@@ -453,6 +453,41 @@ inline int shard_slots(int Le, int qw = 1) {
   return walk_slots(Le, qw * (refine_lp(Le) + walk_scrp(SHARD_CPC_MAX) + walk_bmw(SHARD_CPC_MAX)));
 }
 
+// Sharded ranking against candidate lists (kge_rank_candidates_shard;
+// k_rshard_cand, k_rshard_cand_q).  `ent` points own_lo rows before the shard:
+// only rows [own_lo, own_hi) are read.  Work unit = (query, chunk of cpc list
+// places), chunk-minor on grid.x; the workgroup scores the chunk's OWNED
+// candidates only.  counts are the caller's, zeroed by the call.
+struct CandShardArgs {
+  const float* ent;
+  const float* rel;
+  const float* modulus;
+  const float* trig;         // RotatE: [R, 2, Lr] reference cos | sin of the phases, or null
+  const int64_t* queries;    // [nq, 3]
+  const int64_t* cand;       // [nq, C]; negative: padding
+  int64_t nq, C, E, R;
+  int64_t own_lo, own_hi;    // the owned rows (global ids)
+  int Le, Lr, K;             // K = reduction length (complex: Le / 2)
+  Consts c;
+  int64_t chunks;            // chunks per query
+  int cpc;                   // list places per chunk (the last one may hold fewer)
+  int vec4;                  // rows staged in 16-byte slots (the header's alignment rule)
+  int nslot;                 // half-waves with an LDS row slot (cand_shard_slots)
+  int in_place;              // rows too wide for LDS: q from qref, rows read in place
+  const float* fixed_rows;   // [nq, Le] the reduced fixed-side rows (KGE_RSHARD_ROWS)
+  const float* s_true;       // [nq] the reduced reference-order true scores (KGE_RSHARD_TRUE)
+  float* qref;               // [nq, Le] reference-order q (in_place only; k_rshard_cand_q writes it)
+  int64_t* counts;           // [2, nq] += strictly greater | equal
+  int32_t* err;
+};
+constexpr int CAND_SHARD_CPC_MAX = 1024;  // list places per chunk: the chunk's scores and owned ids sit in LDS
+// a chunk's compacted owned ids (int32) rounded to 4, and the 4 waves' counts of one compaction round
+__host__ __device__ inline int walk_idw(int cpc) { return ((cpc + 3) & ~3) + 4; }
+// fixed: q, the largest score array and the largest id list
+inline int cand_shard_slots(int Le) {
+  return walk_slots(Le, refine_lp(Le) + walk_scrp(CAND_SHARD_CPC_MAX) + walk_idw(CAND_SHARD_CPC_MAX));
+}
+
 // kge_rank_shard_fast: the fast counting pass on a shard-local view (k_rsf_prep,
 // k_rsf_window, the counting tiles, k_rsf_finish).  r is the refinement's
 // argument block over the VIEW: r.ent = the shard's first row, r.E = its row
@@ -517,6 +552,7 @@ struct ModelOps {
   int (*rank_shard)(int mode, int stage, const ShardArgs&, hipStream_t);  // stage: KGE_RSHARD_*
   // kge_rank_shard_fast, stage 0: k_rsf_prep (vec / ns: fixed_rows' slots), 1: k_rsf_window, 2: k_rsf_finish
   int (*rank_shard_fast)(int mode, int vec, int ns, int stage, const ShardFastArgs&, hipStream_t);
+  int (*rank_cand_shard)(int mode, const CandShardArgs&, hipStream_t);
 };
 
 ModelOps model_ops_transe();

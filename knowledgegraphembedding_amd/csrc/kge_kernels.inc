@@ -3103,9 +3103,10 @@ int launch_rank_rel(const RelRankArgs& a, hipStream_t s) {
 
 __device__ __forceinline__ bool rshard_owned(const ShardArgs& a, int64_t e) { return e >= a.own_lo && e < a.own_hi; }
 
-// the query's reference-order q from the reduced fixed-side row (ref_build_q)
-template <int M, int MODE>
-__device__ __forceinline__ void rshard_build_q(const ShardArgs& a, int64_t qi, int64_t r, const Consts& c,
+// the query's reference-order q from the reduced fixed-side row (ref_build_q;
+// A: ShardArgs or CandShardArgs)
+template <int M, int MODE, class A>
+__device__ __forceinline__ void rshard_build_q(const A& a, int64_t qi, int64_t r, const Consts& c,
                                                float* __restrict__ qo) {
   ref_build_q<M, MODE>(a.fixed_rows + qi * a.Le, a.rel + r * a.Lr,
                        (M == ROTATE && a.trig) ? a.trig + r * 2 * a.Lr : nullptr, a.K, c, qo);
@@ -3303,6 +3304,133 @@ int launch_rank_shard(int mode, int stage, const ShardArgs& a, hipStream_t s) {
   return walk_variant(a.in_place, a.vec4, a.Le, [&](auto pq, auto vw) {
     constexpr int PQ = decltype(pq)::value, VW = decltype(vw)::value;
     return launch_b(k_rshard_count<M, HEAD_BATCH, PQ, VW>, k_rshard_count<M, TAIL_BATCH, PQ, VW>);
+  });
+}
+
+// ------------------------- sharded ranking against candidate lists
+// kge_rank_candidates_shard: k_rank_cand's counts over the candidates of every
+// list that fall into the row shard [own_lo, own_hi), against the caller's
+// reduced s_true[q] and with q built from the reduced fixed_rows[q] — the third
+// call of kge_rank_shard's protocol (ROWS, TRUE, then this).  Work unit =
+// (query, chunk of cpc list places), one 256-thread workgroup each, chunk-minor
+// on grid.x.  A rank owns about 1 / world of every list, so the workgroup first
+// COMPACTS its chunk: the 256 threads read the ids coalesced, 256 places a
+// round, and sort each into padding (negative), out of table (≥ E: flagged) or
+// owned; a wave64 ballot and a popcount prefix place the owned ids of a wave,
+// the four waves' counts go through LDS, and the owned ids land in list order
+// in an int32 array in LDS.  A workgroup with no owned candidate leaves before
+// it builds q.  There is no filler row: k_rank_cand's is the true row, which
+// here may be another rank's — the half-waves walk the compacted list alone,
+// each row through the half's LDS slot (walk_rows), every one scored.  Scores
+// land in LDS; the block counts them against s_true[q], nothing skipped (a
+// copy of the true id is a tie), and adds its two integers to counts.
+// Dynamic LDS, floats: [q: Lp][scores: cpc | 2 counters, walk_scrp][owned ids:
+// cpc int32 | 4 wave counts, walk_idw][slots: nslot × Lp].  Rows too wide for q
+// and one slot (in_place) are read where they lie and q comes from
+// k_rshard_cand_q's copy in the workspace (cand_shard_slots: kge_internal.h).
+
+// in_place only: q of every query into the workspace, one block per query
+template <int M, int MODE>
+__global__ __launch_bounds__(256) void k_rshard_cand_q(CandShardArgs a) {
+  const int64_t qi = blockIdx.x;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  if (!query_ok(a.E, a.R, h, r, t)) return;  // (k_rshard_cand flags it)
+  rshard_build_q<M, MODE>(a, qi, r, a.c, a.qref + qi * a.Le);
+}
+
+// PQ, VW: the shape of the row walk (walk_rows, kge_row_walk.inc; walk_variant picks them)
+template <int M, int MODE, int PQ, int VW>
+__global__ __launch_bounds__(256) void k_rshard_cand(CandShardArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float xsm[];
+  constexpr bool IN_PLACE = PQ < 0;
+  const int tid = threadIdx.x, hl = tid & 31, half = tid >> 5, lane = tid & 63, wv = tid >> 6;
+  const int64_t qi = (int64_t)blockIdx.x / a.chunks;
+  const int64_t ch = (int64_t)blockIdx.x - qi * a.chunks;
+  const int64_t h = a.queries[qi * 3], r = a.queries[qi * 3 + 1], t = a.queries[qi * 3 + 2];
+  if (!query_ok(a.E, a.R, h, r, t)) {  // (block-uniform) its counts stay 0 / 0
+    if (ch == 0 && tid == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+    return;
+  }
+  // (the one copy of the constants, made here as k_rank_cand makes it: made behind the compaction,
+  // pRotatE's went to a second scratch slot beside the kernel argument's)
+  Consts c = a.c;
+  if constexpr (M == PROTATE) c.modulus = a.modulus[0];
+  const int Le = a.Le, Lp = refine_lp(Le);
+  const int64_t j0 = ch * a.cpc;
+  const int n = (int)((a.C - j0 < a.cpc) ? (a.C - j0) : a.cpc);  // the chunk's list places, ≥ 1
+  float* scr = xsm + (IN_PLACE ? 0 : Lp);
+  int* cnt_s = reinterpret_cast<int*>(scr + a.cpc);
+  int32_t* ids_l = reinterpret_cast<int32_t*>(scr + walk_scrp(a.cpc));
+  int* wcnt = ids_l + ((a.cpc + 3) & ~3);  // the four waves' owned counts of one round
+  float* slots = scr + walk_scrp(a.cpc) + walk_idw(a.cpc);
+  if (tid < 2) cnt_s[tid] = 0;
+  // the chunk's owned ids, compacted in list order
+  const int64_t* lst = a.cand + qi * a.C + j0;
+  int nown = 0;  // (block-uniform)
+  for (int x0 = 0; x0 < n; x0 += 256) {
+    const int x = x0 + tid;
+    const int64_t e = (x < n) ? lst[x] : (int64_t)-1;
+    const bool mine = e >= a.own_lo && e < a.own_hi;  // (own_hi ≤ E, own_lo ≥ 0)
+    const unsigned long long oob = __ballot(e >= a.E);
+    if (oob && lane == 0) atomicOr(a.err, KGE_DEVERR_INDEX);
+    const unsigned long long bal = __ballot(mine);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    const int c0 = wcnt[0], c1 = wcnt[1], c2 = wcnt[2], c3 = wcnt[3];
+    if (mine) {
+      const int base = nown + (wv > 0 ? c0 : 0) + (wv > 1 ? c1 : 0) + (wv > 2 ? c2 : 0);
+      ids_l[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)e;
+    }
+    nown += c0 + c1 + c2 + c3;
+    __syncthreads();  // (wcnt is rewritten by the next round; ids_l and cnt_s are read below)
+  }
+  if (nown == 0) return;  // no candidate of this chunk is this shard's
+  if constexpr (!IN_PLACE) {
+    rshard_build_q<M, MODE>(a, qi, r, c, xsm);
+    __syncthreads();  // q is read by every half-wave
+  }
+  const float* qs = IN_PLACE ? a.qref + qi * Le : xsm;
+  const int ns = IN_PLACE ? 8 : a.nslot;
+  if (half < ns) {
+    // the half's i-th item is place j = half + ns·i of the compacted list
+    auto item_src = [&](int i, bool&) __attribute__((always_inline)) -> const float* {
+      return a.ent + (int64_t)ids_l[half + ns * i] * Le;
+    };
+    auto score = [&](int j, float* row, bool) __attribute__((always_inline)) {
+      float sc;
+      if constexpr (M == TRANSE && !IN_PLACE) sc = cand_score_transe_lds<MODE>(qs, row, a.K, c, hl);
+      else sc = ref_score_half<M, MODE>(qs, row, a.K, c, hl);
+      if (hl == 0) scr[j] = sc;
+    };
+    walk_rows<PQ, VW>(nown, half, ns, hl, slots + half * Lp, Le, item_src, score);
+  }
+  __syncthreads();
+  count_scores(scr, nown, a.s_true[qi], cnt_s, [](int) { return false; });
+  __syncthreads();
+  if (tid == 0) {  // integer sums: any order of the chunks gives the same counts
+    unsigned long long* cn = reinterpret_cast<unsigned long long*>(a.counts);
+    if (cnt_s[0]) atomicAdd(&cn[qi], (unsigned long long)cnt_s[0]);
+    if (cnt_s[1]) atomicAdd(&cn[a.nq + qi], (unsigned long long)cnt_s[1]);
+  }
+}
+
+template <int M>
+int launch_rank_cand_shard(int mode, const CandShardArgs& a, hipStream_t s) {
+  const int Lp = refine_lp(a.Le);
+  if (a.in_place) {
+    hipLaunchKernelGGL(pick_dir(mode, k_rshard_cand_q<M, HEAD_BATCH>, k_rshard_cand_q<M, TAIL_BATCH>),
+                       dim3((unsigned)a.nq), dim3(256), 0, s, a);
+    const int st = (int)hipGetLastError();
+    if (st) return st;
+  }
+  const size_t lds =
+      sizeof(float) * (size_t)((a.in_place ? 0 : Lp * (1 + a.nslot)) + walk_scrp(a.cpc) + walk_idw(a.cpc));
+  const dim3 grid((unsigned)(a.nq * a.chunks));
+  return walk_variant(a.in_place, a.vec4, a.Le, [&](auto pq, auto vw) {
+    constexpr int PQ = decltype(pq)::value, VW = decltype(vw)::value;
+    hipLaunchKernelGGL(pick_dir(mode, k_rshard_cand<M, HEAD_BATCH, PQ, VW>, k_rshard_cand<M, TAIL_BATCH, PQ, VW>),
+                       grid, dim3(256), lds, s, a);
+    return (int)hipGetLastError();
   });
 }
 
@@ -3692,6 +3820,7 @@ struct ModelTable {
     o.rank_rel = &launch_rank_rel<M>;                                                              \
     o.rank_shard = &launch_rank_shard<M>;                                                          \
     o.rank_shard_fast = &ModelTable<M>::rank_shard_fast;                                           \
+    o.rank_cand_shard = &launch_rank_cand_shard<M>;                                                \
     return o;                                                                                      \
   }                                                                                                \
   }

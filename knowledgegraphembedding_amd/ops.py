@@ -771,6 +771,64 @@ def rank_shard_count(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own
                 workspace=workspace)
 
 
+def rank_candidates_shard_count(desc: _lib.ModelDesc, mode: str, queries: torch.Tensor, own, dev,
+                                fixed_rows: torch.Tensor, s_true: torch.Tensor, cand: torch.Tensor,
+                                counts: torch.Tensor, relation_trig: Optional[torch.Tensor] = None,
+                                workspace: Optional[torch.Tensor] = None) -> None:
+    """The counting call of the sharded ranking against candidate lists
+    (kge_rank_candidates_shard), after rank_shard_rows and rank_shard_true and
+    their all-reduces: `desc` addresses the shard own = (begin, end) by GLOBAL
+    row id as there; from the reduced `fixed_rows` [nq, entity_dim] and
+    `s_true` [nq], counts [2, nq] int64 = the candidates of each query's row of
+    `cand` [nq, C] that this shard owns and that score above (row 0) and equal
+    to (row 1) the true score, in the reference's fp32 score order
+    (rank_candidates' score).  A negative id is padding; nothing else is
+    excluded.  Summed over the ranks (int64 SUM): rank = 1 + counts[0], ties =
+    counts[1] — rank_candidates' on the whole table.  The device error flag is
+    left for the caller's next read (raise_on_device_error): a query with an id
+    out of range counts 0 / 0, a candidate id ≥ nentity is skipped."""
+    name = "rank_candidates_shard_count"
+    if mode not in ("head-batch", "tail-batch"):
+        raise ValueError("mode %s not supported" % mode)
+    if relation_trig is not None:
+        shape = (desc.nrelation, 2, desc.relation_dim)
+        if (tuple(relation_trig.shape) != shape or relation_trig.dtype != torch.float32
+                or not relation_trig.is_contiguous() or relation_trig.device != dev):
+            raise ValueError(f"relation_trig: expected a contiguous float32 {shape} tensor on {dev}")
+        desc = _lib.ModelDesc.from_buffer_copy(desc)
+        desc.relation_trig = relation_trig.data_ptr()
+    q = _idx(queries, dev)
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError(f"queries: {tuple(q.shape)}, expected [nq, 3]")
+    nq = q.shape[0]
+    b, e = int(own[0]), int(own[1])
+    if not 0 <= b <= e <= desc.nentity:
+        raise ValueError(f"own range [{b}, {e}) is not inside [0, {desc.nentity}]")
+    if cand.dim() != 2 or cand.shape[0] != nq or cand.shape[1] < 1 or cand.dtype != torch.int64:
+        raise ValueError(f"cand: {tuple(cand.shape)} {cand.dtype}, expected int64 [{nq}, C] with C >= 1")
+    cd = _idx(cand, dev)
+    C = cd.shape[1]
+
+    def buf(t, what, shape, dtype):
+        if (t is None or t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+
+    sh = _lib.RankCandShardDesc()
+    sh.own_begin, sh.own_end = b, e
+    sh.fixed_rows = buf(fixed_rows, "fixed_rows", (nq, desc.entity_dim), torch.float32)
+    sh.s_true = buf(s_true, "s_true", (nq,), torch.float32)
+    sh.counts = buf(counts, "counts", (2, nq), torch.int64)
+    lib = _lib.load()
+    st = state(dev)
+    ws = workspace if workspace is not None else \
+        st.workspace(lib.kge_rank_candidates_shard_workspace_bytes(desc, nq, C))
+    _lib.check(lib.kge_rank_candidates_shard(desc, _lib.MODE_IDS[mode], sh, q.data_ptr(), nq, cd.data_ptr(), C,
+                                             ws.data_ptr(), ws.numel(), st.err.data_ptr(), _stream(dev)),
+               "kge_rank_candidates_shard")
+    del cd  # (the launches are queued on the stream the caching allocator frees behind)
+
+
 RANK_SHARD_FAST_PATHS = {"auto": 0, "mfma": 1, "tile": 2, "exact": 3}
 
 

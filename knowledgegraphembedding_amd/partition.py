@@ -517,15 +517,100 @@ class EntityRowPartition:
             ops.raise_on_device_error(dev)
         return res
 
+    def _rank_candidates_device(self, model, q, cand, mode, trig):
+        """rank_candidates on device tensors: q a [nq, 3] int64 numpy array,
+        cand [nq, C] int64 on the device; returns (ranks int64, ties int64)
+        device tensors.  The device error flag is left for the caller."""
+        import numpy as np
+        from . import ops
+        dev = self.shard.device
+        desc, own = self._own_desc(model)
+        SUM = dist.ReduceOp.SUM
+        ranks, ties = [], []
+        for b0 in range(0, len(q), self.RANK_BLOCK):
+            qd = torch.from_numpy(np.ascontiguousarray(q[b0:b0 + self.RANK_BLOCK])).to(dev)
+            cb = cand[b0:b0 + self.RANK_BLOCK]
+            nq = qd.shape[0]
+            fixed = torch.empty(nq, self.dim, device=dev)
+            ops.rank_shard_rows(desc, mode, qd, own, dev, fixed)
+            dist.all_reduce(fixed.view(torch.int32), op=SUM, group=self.group)
+            s_true = torch.empty(nq, device=dev)
+            ops.rank_shard_true(desc, mode, qd, own, dev, fixed, s_true, relation_trig=trig)
+            dist.all_reduce(s_true.view(torch.int32), op=SUM, group=self.group)
+            counts = torch.empty(2, nq, dtype=torch.int64, device=dev)
+            ops.rank_candidates_shard_count(desc, mode, qd, own, dev, fixed, s_true, cb, counts, relation_trig=trig)
+            dist.all_reduce(counts, op=SUM, group=self.group)
+            ranks.append(counts[0] + 1)
+            ties.append(counts[1])
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        return (torch.cat(ranks) if ranks else z), (torch.cat(ties) if ties else z)
+
+    def rank_candidates(self, model, triples, candidates, mode, relation_trig=None):
+        """Per-query ranks and tie counts (numpy int64, int32) among per-query
+        candidate lists, as KGEModel.rank_candidates — the same arguments, the
+        same result — with the table used IN PLACE: every rank scores only the
+        candidates whose rows it owns (kge_rank_candidates_shard) and
+        ``materialize()`` is not called.  Collective: every rank passes the
+        same triples and lists and gets the same result.  Per block of
+        RANK_BLOCK queries, three all-reduces on the group, as rank_queries:
+        the fixed side's rows and the true scores from their owners (int32),
+        then the int64 counts.  A candidate's score does not depend on which
+        rank computes it, so the summed counts are the one-table ranks and
+        ties bit for bit (RotatE with the reference's rotation table, pRotatE
+        with the correctly rounded device sin, as there).  A query whose three
+        ids are in range but whose row of `candidates` is all padding has rank
+        1, ties 0."""
+        import numpy as np
+        from . import ops
+        if mode not in ('head-batch', 'tail-batch'):
+            raise ValueError('mode %s not supported' % mode)
+        dev = self.shard.device
+        q = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+        cand = candidates if isinstance(candidates, torch.Tensor) else \
+            torch.from_numpy(np.array(candidates, dtype=np.int64, order='C'))  # (a copy: the input may be read-only)
+        if cand.dim() != 2 or cand.shape[0] != len(q) or cand.shape[1] < 1:
+            raise ValueError(f"candidates: {tuple(cand.shape)}, expected [{len(q)}, C] with C >= 1")
+        cand = cand.to(dev, torch.int64)
+        with torch.no_grad():
+            ranks, ties = self._rank_candidates_device(model, q, cand, mode, model._rank_rotation(dev, relation_trig))
+            res =ranks.cpu().numpy(), ties.cpu().numpy().astype(np.int32)
+            ops.raise_on_device_error(dev)
+        return res
+
+    def _sampled_test_step(self, model, test_triples, all_true_triples, n_cand):
+        """test_step under KGE_EVAL_SHARD_CANDIDATES: KGEModel.test_step's
+        sampled evaluation (KGE_EVAL_CANDIDATES) in place.  The draws are
+        sampled_eval_blocks': they depend on the seed alone, so every rank
+        draws the same lists."""
+        from . import ops
+        from .model import _check_eval_candidates, _rank_metrics
+        _check_eval_candidates(n_cand, self.nentity)  # (before any launch)
+        dev = self.shard.device
+        ranks_seq = []
+        with torch.no_grad():
+            trig = model._rank_rotation(dev)
+            out = [self._rank_candidates_device(model, q, cand, mode, trig)[0]
+                   for mode, q, cand in model.sampled_eval_blocks(test_triples, all_true_triples, n_cand)]
+            for ranks in out:  # head-batch blocks, then tail-batch
+                ranks_seq.extend(ranks.cpu().numpy().tolist())
+            ops.raise_on_device_error(dev)
+        return _rank_metrics(ranks_seq)
+
     def test_step(self, model, test_triples, all_true_triples, args):
         """KGEModel.test_step's filtered metrics (model.py:315-429: head-batch
         queries, then tail-batch) from rank_queries — collective, the same
-        dict on every rank, the whole table on none."""
+        dict on every rank, the whole table on none.  With
+        KGE_EVAL_SHARD_CANDIDATES=N in the environment: the sampled metrics of
+        KGEModel.test_step under KGE_EVAL_CANDIDATES=N (every query against N
+        drawn candidates, KGE_EVAL_SEED as there) from rank_candidates' kernel."""
         from .filters import FilterIndex, triples_array
         from .model import _rank_metrics
         if getattr(args, 'countries', False):
             raise ValueError("the sharded evaluation ranks entities; --countries scores regions with forward")
         model.eval()
+        n_cand = int(os.environ.get("KGE_EVAL_SHARD_CANDIDATES", "0") or 0)
+        if n_cand > 0:
+            return self._sampled_test_step(model, test_triples, all_true_triples, n_cand)
         index = FilterIndex(all_true_triples, self.nentity, model.nrelation, device=self.shard.device)
         triples = triples_array(test_triples)
         ranks_seq = []

@@ -22,6 +22,11 @@ Differences from the reference, all on the execution side:
     evaluates the gathered table alone, as before.  Not with --countries,
     KGE_EVAL_CANDIDATES or KGE_EVAL_RELATIONS; pRotatE then ranks with the
     correctly rounded device sin, not the reference library's.
+    KGE_EVAL_SHARD_CANDIDATES=N with it: the sharded evaluation is SAMPLED —
+    every query is ranked against N drawn candidates, the metrics of
+    KGE_EVAL_CANDIDATES=N on the gathered table (the same draws under the same
+    KGE_EVAL_SEED), each rank scoring the candidates whose rows it owns
+    (kge_rank_candidates_shard).  Unset or 0: every entity is ranked.
 """
 from __future__ import absolute_import, division, print_function
 
@@ -305,9 +310,10 @@ def eval_sharded_requested(args) -> bool:
         return False
     if getattr(args, 'countries', False):
         raise ValueError('KGE_EVAL_SHARDED: --countries scores regions with forward, not a ranking over the table')
-    for var in ('KGE_EVAL_CANDIDATES', 'KGE_EVAL_RELATIONS'):
+    for var, hint in (('KGE_EVAL_CANDIDATES', '; the sharded sampled evaluation is KGE_EVAL_SHARD_CANDIDATES=N'),
+                      ('KGE_EVAL_RELATIONS', '')):
         if (os.environ.get(var, '0') or '0') != '0':
-            raise ValueError('KGE_EVAL_SHARDED cannot be combined with %s (unset one of them)' % var)
+            raise ValueError('KGE_EVAL_SHARDED cannot be combined with %s (unset one of them%s)' % (var, hint))
     return True
 
 
